@@ -4,7 +4,12 @@ training throughput on MD17-shape molecules (BASELINE.json configs[1]).
 Contract (driver): `python bench.py --gpus N --steps K --warmup W` runs
 W untimed warmup steps then times exactly K steps bracketed by
 barrier + torch.cuda.synchronize on both sides; rank 0 prints ONE JSON
-line with the whole-job aggregate graphs/sec.
+line with the whole-job aggregate graphs/sec and `ms_per_step`.  A
+plain run does nothing beyond that; `--full` is where measurements
+beyond the headline figure belong.  `--dump-outputs DIR` writes what
+the timed train() call returned and what its last step computed as
+DIR/<name>.npy; model, data and batch order are seeded, so two builds
+run with the same arguments see identical inputs.
 
 Launched for N>1 as: python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
@@ -252,19 +257,29 @@ def make_loaders(rank, steps, warmup, batch, use_cuda,
     from hydragnn_amd.utils.datasets.synthetic import (
         md17_shape_dataset_fast)
 
-    total = (steps + warmup) * batch
-    ds = md17_shape_dataset_fast(
-        total, radius=MODEL_CONFIG["radius"], seed=seed + rank * 1000003)
-    node_cap, edge_cap = compute_static_caps(ds, batch,
-                                             sequential=True)
-    coll = StaticShapeCollater(node_cap, edge_cap,
-                               pad_spacing=4 * MODEL_CONFIG["radius"])
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # collating 4096-graph batches is CPU-heavy: measured +12% g/s
     # going 8 -> 16 workers at b4096 (256-core box)
     nw = int(os.environ.get(
         "HYDRAGNN_BENCH_WORKERS",
         str(min(16, max(2, (os.cpu_count() or 8) // (4 * world))))))
+    total = (steps + warmup) * batch
+    # set-up cost grows with steps: evaluate the molecule chunks in
+    # nw processes and leave the per-molecule Data objects to the
+    # loader workers; the samples are the same either way
+    ds = md17_shape_dataset_fast(
+        total, radius=MODEL_CONFIG["radius"], seed=seed + rank * 1000003,
+        lazy=True, workers=nw)
+    # the first timed batches are wanted before a worker could build
+    # their samples (all workers start at once, and a step is shorter
+    # than one batch's worth of Data objects): build those here, so
+    # the timed loop opens as it does with an eager list
+    ds.materialize(range(warmup * batch,
+                         min(total, (warmup + 3) * batch)))
+    node_cap, edge_cap = compute_static_caps(ds.sizes(), batch,
+                                             sequential=True)
+    coll = StaticShapeCollater(node_cap, edge_cap,
+                               pad_spacing=4 * MODEL_CONFIG["radius"])
     kwargs = dict(batch_size=batch, collate_fn=coll, shuffle=False,
                   drop_last=True, num_workers=nw,
                   pin_memory=use_cuda,
@@ -275,12 +290,66 @@ def make_loaders(rank, steps, warmup, batch, use_cuda,
     return warm, timed
 
 
+# --dump-outputs writes at most this many bytes in all
+DUMP_BYTE_CAP = 64 * 2**20
+
+
+def record_last_loss(model):
+    """Keep handles on the loss tensors of the most recent step.  On
+    the captured path these are the graph's static outputs, so after
+    the last replay they hold the last step's values."""
+    base = model.module if hasattr(model, "module") else model
+    last = {}
+    orig = base.energy_force_loss
+
+    def energy_force_loss(*a, **k):
+        loss, tasks_loss = orig(*a, **k)
+        last["loss"] = loss.detach()
+        last["tasks_loss"] = [t.detach() for t in tasks_loss]
+        return loss, tasks_loss
+
+    base.energy_force_loss = energy_force_loss
+    return last
+
+
+def dump_outputs(out_dir, tensors):
+    """Write {name: tensor} as out_dir/<name>.npy (float32; float64
+    stays float64).  Arrays that would not fit an equal share of
+    DUMP_BYTE_CAP are reduced to a fixed, seeded sample of their
+    flattened elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTE_CAP // max(1, len(tensors))
+    for name, t in tensors.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        a = t.cpu().numpy()
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.random.default_rng(0).choice(a.size, keep,
+                                                  replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--gpus", type=int, default=1)
     parser.add_argument("--steps", type=int, default=20)
     parser.add_argument("--warmup", type=int, default=5)
     parser.add_argument("--batch", type=int, default=LOCAL_BATCH)
+    parser.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="after the timed steps, write what train() returned and "
+             "what its last step computed (loss terms, gradients, "
+             "updated parameters) as DIR/<name>.npy")
+    parser.add_argument(
+        "--full", action="store_true",
+        help="also run the measurements beyond the headline figure. "
+             "The flagship benchmark has none of its own (per-config, "
+             "step-only and scaling numbers come from scripts/ and "
+             "run-scripts/), so today this changes nothing")
     args = parser.parse_args()
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -306,6 +375,11 @@ def main():
     from hydragnn_amd.utils.distributed import distributed_model_wrapper
 
     precision = os.environ.get("HYDRAGNN_BENCH_PRECISION", PRECISION)
+    # data first: its generator forks helper processes, which is best
+    # done before this process has touched the GPU
+    warm_loader, timed_loader = make_loaders(
+        rank, args.steps, args.warmup, args.batch, use_cuda,
+        precision=precision)
     model = build_model(device, precision=precision)
     # FusedAdamW flattens params into one buffer (single-kernel step);
     # construct BEFORE the DDP wrap so reducer bucket views are built
@@ -323,10 +397,7 @@ def main():
         # DDP's construction-time broadcast may have overwritten the
         # flat params; keep the fp32 master in sync
         optimizer.master.copy_(optimizer.flat_param.float())
-
-    warm_loader, timed_loader = make_loaders(
-        rank, args.steps, args.warmup, args.batch, use_cuda,
-        precision=precision)
+    last = record_last_loss(model) if args.dump_outputs else None
 
     if warm_loader is not None:
         train(warm_loader, model, optimizer, 0, precision=precision)
@@ -350,12 +421,27 @@ def main():
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    train(timed_loader, model, optimizer, 0, precision=precision)
+    train_error, train_tasks_error = train(
+        timed_loader, model, optimizer, 0, precision=precision)
     if use_cuda:
         torch.cuda.synchronize()
     if dist.is_initialized():
         dist.barrier()
     t1 = time.perf_counter()
+
+    if args.dump_outputs and rank == 0:
+        params = [p for p in model.parameters() if p.grad is not None]
+        dump_outputs(args.dump_outputs, {
+            "train_error": train_error,
+            "train_tasks_error": train_tasks_error,
+            "last_step_loss": last["loss"].reshape(1),
+            "last_step_tasks_loss": torch.stack(
+                [t.reshape(()) for t in last["tasks_loss"]]),
+            "last_step_grads": torch.cat(
+                [p.grad.reshape(-1) for p in params]),
+            "params": torch.cat(
+                [p.reshape(-1) for p in model.parameters()]),
+        })
 
     elapsed = t1 - t0
     # MAX over ranks

@@ -74,7 +74,9 @@ def main():
         with torch.no_grad():
             total, count = 0.0, 0
             from hydragnn_amd.train import get_head_indices
+            device = next(core.parameters()).device
             for batch in loaders[1]:
+                batch = batch.to(device)
                 pred = core(batch)
                 loss, _ = core.loss(pred, batch.y,
                                     get_head_indices(core, batch))

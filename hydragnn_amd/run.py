@@ -64,13 +64,15 @@ def run_training(config: Union[str, dict], dataset=None,
                                 verbosity=verbosity, use_gpu=use_gpu)
     optimizer = select_optimizer(
         model, config["NeuralNetwork"]["Training"]["Optimizer"])
-    # restart support (reference model.py:204-211)
-    load_existing_model_config(
-        model, config["NeuralNetwork"]["Training"], optimizer=optimizer)
     model = distributed_model_wrapper(
         model, verbosity=verbosity,
         sync_batch_norm=config["NeuralNetwork"]["Architecture"].get(
             "SyncBatchNorm", False))
+    # restart support (reference model.py:204-211); after the move to
+    # the training device, so the restored optimizer state lands on
+    # the same device as the parameters
+    load_existing_model_config(
+        model, config["NeuralNetwork"]["Training"], optimizer=optimizer)
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(
         optimizer, mode="min", factor=0.5, patience=5)
     writer = get_summary_writer(log_name)

@@ -12,6 +12,7 @@ from __future__ import annotations
 import math
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from ...data import Data
@@ -149,6 +150,120 @@ def md17_shape_dataset(
     return dataset
 
 
+def _md17_fast_chunk(args):
+    """Push-apart, LJ targets and dst-major edges for one chunk of
+    drawn positions [m, n, 3] -- a pure function of the draw, so chunks
+    can be evaluated in any process.  Takes and returns numpy arrays
+    (pos, energy, forces, per-edge dst*n+src, per-molecule edge
+    counts), which cross a process boundary by value."""
+    pos, radius, min_dist, max_push = args
+    pos = torch.from_numpy(pos)
+    m, n = pos.shape[0], pos.shape[1]
+    eye = torch.eye(n, dtype=torch.bool)
+    for _ in range(max_push):
+        d = torch.cdist(pos, pos) + eye * 10
+        mind = d.flatten(1).min(dim=1).values
+        scale = torch.where(mind > min_dist,
+                            torch.ones(m), torch.full((m,), 1.25))
+        if (scale == 1.0).all():
+            break
+        pos = pos * scale.view(-1, 1, 1)
+    posd = pos.double()
+    # _lj_energy_forces convention: vec = pos[dst] - pos[src];
+    # vec[b, src, dst, :] = pos[b, dst] - pos[b, src]
+    vec = posd.unsqueeze(1) - posd.unsqueeze(1).transpose(1, 2)
+    r2 = (vec * vec).sum(-1).clamp(min=1e-12)
+    within = (r2 < radius * radius) & ~eye
+    # soft-core at min_dist: the 1.25x push loop cannot separate
+    # near-coincident pairs (a multiplicative rescale leaves tiny
+    # distances tiny), and an unclamped LJ at r~0.05 produces
+    # ~1e15 force targets that blow the initial loss up to ~1e30
+    # (observed tripping the captured-step sanity check).
+    r2 = r2.clamp(min=min_dist * min_dist)
+    sigma2 = 1.0
+    inv_r2 = sigma2 / r2
+    inv_r6 = inv_r2 ** 3
+    inv_r12 = inv_r6 ** 2
+    epsilon = 0.05
+    e_pair = 4.0 * epsilon * (inv_r12 - inv_r6) * within
+    energy = 0.5 * e_pair.sum(dim=(1, 2))
+    coef = (24.0 * epsilon * (2.0 * inv_r12 - inv_r6) / r2) * within
+    # force on dst: sum over src of coef * vec  -> reduce dim 1
+    forces = (coef.unsqueeze(-1) * vec).sum(dim=1)
+    # dst-major edge extraction: index mask as [dst, src]
+    mask_ds = within.transpose(1, 2)  # [b, dst, src]
+    nz = mask_ds.reshape(m, -1).nonzero(as_tuple=False)
+    b_idx, flat = nz[:, 0], nz[:, 1]
+    counts = torch.bincount(b_idx, minlength=m)
+    return (pos.numpy(), energy.numpy(), forces.numpy(),
+            flat.to(torch.int32).numpy(), counts.numpy())
+
+
+class _MoleculeSize:
+    __slots__ = ("num_nodes", "num_edges")
+
+    def __init__(self, num_nodes, num_edges):
+        self.num_nodes = num_nodes
+        self.num_edges = num_edges
+
+
+class MD17ShapeMolecules(torch.utils.data.Dataset):
+    """The samples of md17_shape_dataset_fast held as flat per-field
+    tensors.  Each Data object is built on access, so a DataLoader
+    builds them in its workers; ``sizes()`` gives per-sample node and
+    edge counts (compute_static_caps) without building any, and
+    ``materialize`` builds chosen samples ahead of time."""
+
+    def __init__(self, z, x_feat, parts, dtype):
+        self.z, self.x_feat = z, x_feat
+        self.n = z.numel()
+        pos, energy, forces, self.flat, counts = [
+            torch.from_numpy(np.concatenate([p[i] for p in parts]))
+            for i in range(5)]
+        self.pos = pos.to(dtype)
+        self.energy = energy.to(dtype)
+        self.forces = forces.to(dtype)
+        offs = torch.zeros(counts.numel() + 1, dtype=torch.long)
+        offs[1:] = counts.cumsum(0)
+        self._offs = offs.tolist()
+        self._built = {}
+
+    def __len__(self):
+        return len(self._offs) - 1
+
+    def sizes(self):
+        o = self._offs
+        return [_MoleculeSize(self.n, o[b + 1] - o[b])
+                for b in range(len(self))]
+
+    def materialize(self, indices):
+        for b in indices:
+            self._built[b] = self._build(b)
+
+    def _build(self, b):
+        n = self.n
+        flat = self.flat[self._offs[b]:self._offs[b + 1]].long()
+        dsts, srcs = flat // n, flat % n
+        d = Data(
+            x=self.x_feat.clone(),
+            z=self.z.clone(),
+            pos=self.pos[b].clone(),
+            edge_index=torch.stack([srcs, dsts], dim=0),
+            energy=self.energy[b].view(1, 1).clone(),
+            forces=self.forces[b].clone(),
+            y=(self.energy[b] / n).view(1, 1).clone(),
+        )
+        d.num_nodes = n
+        return d
+
+    def __getitem__(self, b):
+        if not -len(self) <= b < len(self):
+            raise IndexError(b)
+        b %= len(self)
+        d = self._built.get(b)
+        return d if d is not None else self._build(b)
+
+
 def md17_shape_dataset_fast(
     num_samples: int,
     radius: float = 7.0,
@@ -159,75 +274,39 @@ def md17_shape_dataset_fast(
     chunk: int = 2048,
     min_dist: float = 0.7,
     max_push: int = 3,
+    lazy: bool = False,
+    workers: int = 0,
 ):
     """Vectorized md17_shape_dataset: generates molecules in batched
     chunks (one cdist/LJ evaluation per chunk instead of per molecule)
     so bench-scale datasets (tens of thousands of samples) build in
     seconds.  Same distribution as md17_shape_dataset; edge lists are
     dst-major sorted (CSR-friendly).  No neighbor cap: aspirin-shape
-    molecules have at most n-1=20 neighbours < the bench cap of 30."""
+    molecules have at most n-1=20 neighbours < the bench cap of 30.
+
+    ``workers`` > 1 evaluates the chunks in that many forked processes.
+    The positions are still drawn in order from the one seeded
+    generator, so the samples do not depend on it.  ``lazy=True``
+    returns an MD17ShapeMolecules instead of the list of its items."""
     g = torch.Generator().manual_seed(seed)
     z = torch.tensor(list(species), dtype=torch.long)
     n = z.numel()
     x_feat = z.to(dtype).view(-1, 1)
-    eye = torch.eye(n, dtype=torch.bool)
-    out = []
+    jobs = []
     for start in range(0, num_samples, chunk):
         m = min(chunk, num_samples - start)
         pos = (torch.rand(m, n, 3, generator=g) - 0.5) * 2 * spread
-        for _ in range(max_push):
-            d = torch.cdist(pos, pos) + eye * 10
-            mind = d.flatten(1).min(dim=1).values
-            scale = torch.where(mind > min_dist,
-                                torch.ones(m), torch.full((m,), 1.25))
-            if (scale == 1.0).all():
-                break
-            pos = pos * scale.view(-1, 1, 1)
-        posd = pos.double()
-        # _lj_energy_forces convention: vec = pos[dst] - pos[src];
-        # vec[b, src, dst, :] = pos[b, dst] - pos[b, src]
-        vec = posd.unsqueeze(1) - posd.unsqueeze(1).transpose(1, 2)
-        r2 = (vec * vec).sum(-1).clamp(min=1e-12)
-        within = (r2 < radius * radius) & ~eye
-        # soft-core at min_dist: the 1.25x push loop cannot separate
-        # near-coincident pairs (a multiplicative rescale leaves tiny
-        # distances tiny), and an unclamped LJ at r~0.05 produces
-        # ~1e15 force targets that blow the initial loss up to ~1e30
-        # (observed tripping the captured-step sanity check).
-        r2 = r2.clamp(min=min_dist * min_dist)
-        sigma2 = 1.0
-        inv_r2 = sigma2 / r2
-        inv_r6 = inv_r2 ** 3
-        inv_r12 = inv_r6 ** 2
-        epsilon = 0.05
-        e_pair = 4.0 * epsilon * (inv_r12 - inv_r6) * within
-        energy = 0.5 * e_pair.sum(dim=(1, 2))
-        coef = (24.0 * epsilon * (2.0 * inv_r12 - inv_r6) / r2) * within
-        # force on dst: sum over src of coef * vec  -> reduce dim 1
-        forces = (coef.unsqueeze(-1) * vec).sum(dim=1)
-        # dst-major edge extraction: index mask as [dst, src]
-        mask_ds = within.transpose(1, 2)  # [b, dst, src]
-        nz = mask_ds.reshape(m, -1).nonzero(as_tuple=False)
-        b_idx, flat = nz[:, 0], nz[:, 1]
-        dsts, srcs = flat // n, flat % n
-        counts = torch.bincount(b_idx, minlength=m)
-        offs = torch.zeros(m + 1, dtype=torch.long)
-        offs[1:] = counts.cumsum(0)
-        pos_f = pos.to(dtype)
-        energy_f = energy.to(dtype)
-        forces_f = forces.to(dtype)
-        for b in range(m):
-            lo, hi = int(offs[b]), int(offs[b + 1])
-            ei = torch.stack([srcs[lo:hi], dsts[lo:hi]], dim=0)
-            d = Data(
-                x=x_feat.clone(),
-                z=z.clone(),
-                pos=pos_f[b].clone(),
-                edge_index=ei,
-                energy=energy_f[b].view(1, 1).clone(),
-                forces=forces_f[b].clone(),
-                y=(energy_f[b] / n).view(1, 1).clone(),
-            )
-            d.num_nodes = n
-            out.append(d)
-    return out
+        jobs.append((pos.numpy(), radius, min_dist, max_push))
+    if not jobs:
+        return []
+    if workers > 1 and len(jobs) > 1:
+        import multiprocessing as mp
+        # one thread per process, as in DataLoader workers
+        with mp.get_context("fork").Pool(
+                min(workers, len(jobs)), initializer=torch.set_num_threads,
+                initargs=(1,)) as pool:
+            parts = pool.map(_md17_fast_chunk, jobs)
+    else:
+        parts = [_md17_fast_chunk(j) for j in jobs]
+    ds = MD17ShapeMolecules(z, x_feat, parts, dtype)
+    return ds if lazy else [ds[b] for b in range(len(ds))]

@@ -12,6 +12,11 @@ pytestmark = pytest.mark.mpi
 
 
 def _init(rank, world_size, port):
+    # CPU/gloo ranks by design: on a host that has a GPU, keep the
+    # spawned ranks off it (FSDP2's default mesh and get_device() would
+    # otherwise put every rank's shards on device 0 behind a gloo group)
+    os.environ["HIP_VISIBLE_DEVICES"] = ""
+    os.environ["CUDA_VISIBLE_DEVICES"] = ""
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     os.environ["RANK"] = str(rank)
@@ -183,8 +188,10 @@ def test_bench_two_rank_gloo():
          "--master-port", "29541", os.path.join(repo, "bench.py"),
          "--gpus", "2", "--steps", "2", "--warmup", "1",
          "--batch", "4"]
+    # CPU/gloo: two ranks must not share the one GPU a host may have
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600,
-                       cwd=repo)
+                       cwd=repo, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     import json
     line = [ln for ln in r.stdout.splitlines()

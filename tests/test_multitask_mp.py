@@ -17,6 +17,8 @@ def _worker(rank, world_size, port, q):
             "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port),
             "RANK": str(rank), "WORLD_SIZE": str(world_size),
             "LOCAL_RANK": str(rank),
+            # CPU/gloo ranks by design: keep them off a host's GPU
+            "HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": "",
         })
         dist.init_process_group("gloo", rank=rank, world_size=world_size)
         import sys

@@ -58,6 +58,33 @@ def test_pad_batch_loss_grad_equivalence():
     assert (g1 - g2).abs().max() < 1e-5 * max(1.0, g1.abs().max())
 
 
+def test_fast_dataset_lazy_and_pooled_are_the_same_samples():
+    """The lazy dataset and the chunk pool only move where the work is
+    done: every field of every sample equals the eager serial list bit
+    for bit, over several chunks with a ragged last one, whether a
+    sample was built ahead of time or on access."""
+    ref = md17_shape_dataset_fast(70, seed=5, chunk=16)
+    lazy = md17_shape_dataset_fast(70, seed=5, chunk=16, lazy=True,
+                                   workers=3)
+    lazy.materialize(range(10, 30))
+    assert lazy[12] is lazy[12] and lazy[40] is not lazy[40]
+    pooled = md17_shape_dataset_fast(70, seed=5, chunk=16, workers=3)
+    assert len(lazy) == len(pooled) == len(ref) == 70
+    sizes = lazy.sizes()
+    for i, r in enumerate(ref):
+        assert (sizes[i].num_nodes, sizes[i].num_edges) == \
+            (r.num_nodes, r.num_edges)
+        for other in (lazy[i], pooled[i]):
+            assert other.num_nodes == r.num_nodes
+            for k in ("x", "z", "pos", "edge_index", "energy", "forces",
+                      "y"):
+                assert other[k].dtype == r[k].dtype, k
+                assert torch.equal(other[k], r[k]), k
+    with pytest.raises(IndexError):
+        lazy[70]
+    assert md17_shape_dataset_fast(0) == []
+
+
 def test_static_collater_fixed_shapes():
     ds = md17_shape_dataset_fast(32, seed=9)
     nc, ec = compute_static_caps(ds, 8)
@@ -182,6 +209,48 @@ def test_bench_trainloop_cpu():
     out = json.loads(line)
     assert out["value"] > 0 and out["steps"] == 2
     assert out["n_gpus"] == 1
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes train()'s results and the last step's
+    loss terms, gradients and parameters as float32 .npy files; the
+    seeded inputs make two runs agree output for output.  --full is
+    accepted and leaves the result line's fields in place."""
+    import numpy as np
+    env = dict(os.environ, HYDRAGNN_BENCH_PRECISION="fp32",
+               HYDRAGNN_BENCH_WORKERS="0", MASTER_ADDR="127.0.0.1",
+               HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out_dir = tmp_path / name
+        r = subprocess.run(
+            [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+             "--steps", "2", "--warmup", "0", "--batch", "4",
+             "--dump-outputs", str(out_dir)] + extra,
+            capture_output=True, text=True, timeout=420, cwd=REPO,
+            env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        for key in ("metric", "value", "unit", "higher_is_better",
+                    "dtype"):
+            assert key in out
+        dumps.append({p.stem: np.load(p)
+                      for p in sorted(out_dir.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"train_error", "train_tasks_error",
+                      "last_step_loss", "last_step_tasks_loss",
+                      "last_step_grads", "params"}
+    assert a["last_step_tasks_loss"].shape == (3,)
+    assert a["last_step_grads"].shape == a["params"].shape
+    assert np.abs(a["last_step_grads"]).max() > 0
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        # identical inputs; only the order of fp32 sums may differ
+        assert np.allclose(v, b[k], rtol=1e-4,
+                           atol=1e-5 * np.abs(v).max()), k
 
 
 # (2-rank torchrun coverage of the same path lives in

@@ -14,6 +14,8 @@
 // the contraction: gradients of a trilinear form are trilinear forms
 // with role-permuted entry tables (see ops/etp.py), so force training
 // (create_graph=True double backward) never leaves this kernel family.
+// The sweep kernels at the end of the file produce several of those
+// derivatives per launch, with every row staged once.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -455,6 +457,229 @@ __global__ void etp_reduce_l1_kernel(
   }
 }
 
+// ---------------------------------------------------------------------
+// Sweep family: several derivatives of the quadrilinear form
+//   Q(a,b,g,o) = sum_k coef_k a[a_k] b[b_k] g[g_k] o[o_k]
+// in ONE walk of the entry table, every row staged once.  Slot bits:
+// a=1, b=2, g=4, o=8.
+// ---------------------------------------------------------------------
+
+// Per-thread LDS slice layout, shared by host (footprint) and device:
+// four primal rows, then the present tangent rows, then the masked
+// output rows; odd word stride as in etp_general_kernel.
+struct SweepLayout {
+  int p[4], t[4], o[4], stride;
+  __host__ __device__ SweepLayout(int da, int db, int dg, int do_,
+                                  int tmask, int omask) {
+    const int d[4] = {da, db, dg, do_};
+    int off = 0;
+    for (int s = 0; s < 4; ++s) { p[s] = off; off += d[s]; }
+    for (int s = 0; s < 4; ++s) {
+      t[s] = off;
+      if (tmask & (1 << s)) off += d[s];
+    }
+    for (int s = 0; s < 4; ++s) {
+      o[s] = off;
+      if (omask & (1 << s)) off += d[s];
+    }
+    stride = off | 1;
+  }
+};
+
+// Row moves between global memory and the LDS slice.  With `vec` (the
+// host found every base 16-byte aligned) a row whose length allows it
+// moves in packs of 4 or 2 elements (8/4-byte accesses for 2-byte
+// types, 16/8 for fp32, 16 for fp64) instead of one access per element.
+template <typename T, int W> struct alignas(sizeof(T) * W) RowPack {
+  T v[W];
+};
+
+template <int W, typename T, typename ACC>
+__device__ inline void load_packs(const T* __restrict__ p, ACC* dst,
+                                  int d) {
+  for (int k = 0; k < d; k += W) {
+    const RowPack<T, W> q = *reinterpret_cast<const RowPack<T, W>*>(p + k);
+    for (int j = 0; j < W; ++j) dst[k + j] = (ACC)q.v[j];
+  }
+}
+
+template <int W, typename T, typename ACC>
+__device__ inline void store_packs(T* __restrict__ p, const ACC* src,
+                                   int d) {
+  for (int k = 0; k < d; k += W) {
+    RowPack<T, W> q;
+    for (int j = 0; j < W; ++j) q.v[j] = (T)src[k + j];
+    *reinterpret_cast<RowPack<T, W>*>(p + k) = q;
+  }
+}
+
+template <typename T, typename ACC>
+__device__ inline void load_row(const T* __restrict__ p, ACC* dst, int d,
+                                bool vec) {
+  constexpr int WMAX = sizeof(T) == 8 ? 2 : 4;
+  if (vec && d % WMAX == 0) {
+    load_packs<WMAX>(p, dst, d);
+  } else if (vec && d % 2 == 0) {
+    load_packs<2>(p, dst, d);
+  } else {
+    for (int k = 0; k < d; ++k) dst[k] = (ACC)p[k];
+  }
+}
+
+template <typename T, typename ACC>
+__device__ inline void store_row(T* __restrict__ p, const ACC* src, int d,
+                                 bool vec) {
+  constexpr int WMAX = sizeof(T) == 8 ? 2 : 4;
+  if (vec && d % WMAX == 0) {
+    store_packs<WMAX>(p, src, d);
+  } else if (vec && d % 2 == 0) {
+    store_packs<2>(p, src, d);
+  } else {
+    for (int k = 0; k < d; ++k) p[k] = (T)src[k];
+  }
+}
+
+// ORDER 1: out_s = dQ/ds at the primals, for each s in omask.
+// ORDER 2: out_s = sum over r != s with a tangent present of dQ/ds with
+//          slot r replaced by its tangent (absent tangents count as 0).
+// Same mapping as etp_general_kernel: one thread per (row, channel),
+// uniform entry walk, fp32/fp64 accumulation in the LDS slice.  The b
+// output is per row: with nch == 64 one wave is exactly one row, so a
+// shuffle reduction ends in one store in the output dtype (outB);
+// otherwise per-thread partials go to a zeroed accumulator (outB_acc)
+// with atomics and the host casts.
+// OMASK / TMASK >= 0 fix the output and tangent masks at compile time
+// (the masks training uses), so the entry loop is one straight block;
+// -1 reads them from the arguments.
+template <typename T, int ORDER, int OMASK, int TMASK>
+__global__ void etp_sweep_kernel(
+    const T* __restrict__ pA, const T* __restrict__ pB,
+    const T* __restrict__ pG, const T* __restrict__ pO,
+    const T* __restrict__ tA, const T* __restrict__ tB,
+    const T* __restrict__ tG, const T* __restrict__ tO,
+    T* __restrict__ outA, T* __restrict__ outB,
+    typename acc_of<T>::type* __restrict__ outB_acc,
+    T* __restrict__ outG, T* __restrict__ outO,
+    const int4* __restrict__ entries,
+    const float* __restrict__ coefs, int n_ent,
+    long rows, int nch, int da, int db, int dg, int do_, int omask,
+    bool vec) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using ACC = typename acc_of<T>::type;
+  const int om = OMASK >= 0 ? OMASK : omask;
+  const int tm = ORDER == 1 ? 0
+                 : TMASK >= 0 ? TMASK
+                 : (tA ? 1 : 0) | (tB ? 2 : 0) | (tG ? 4 : 0) | (tO ? 8 : 0);
+  const bool hta = tm & 1, htb = tm & 2, htg = tm & 4, hto = tm & 8;
+  const SweepLayout L(da, db, dg, do_, tm, om);
+  ACC* slices = reinterpret_cast<ACC*>(smem);
+  // table after the slices, on a 16-byte boundary for the int4 reads
+  size_t slice_bytes =
+      ((size_t)blockDim.x * L.stride * sizeof(ACC) + 15) & ~(size_t)15;
+  int4* ent_lds = reinterpret_cast<int4*>(smem + slice_bytes);
+  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
+  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
+    ent_lds[k] = entries[k];
+    coef_lds[k] = coefs[k];
+  }
+
+  const long NC = rows * nch;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < NC;
+  const long e = i / nch;
+  ACC* my = slices + (size_t)threadIdx.x * L.stride;
+  ACC* xa = my + L.p[0];
+  ACC* xb = my + L.p[1];
+  ACC* xg = my + L.p[2];
+  ACC* xo = my + L.p[3];
+  ACC* ya = my + L.t[0];
+  ACC* yb = my + L.t[1];
+  ACC* yg = my + L.t[2];
+  ACC* yo = my + L.t[3];
+  ACC* ra = my + L.o[0];
+  ACC* rb = my + L.o[1];
+  ACC* rg = my + L.o[2];
+  ACC* ro = my + L.o[3];
+  if (valid) {
+    load_row(pA + i * da, xa, da, vec);
+    load_row(pB + e * db, xb, db, vec);
+    load_row(pG + i * dg, xg, dg, vec);
+    load_row(pO + i * do_, xo, do_, vec);
+    if (hta) load_row(tA + i * da, ya, da, vec);
+    if (htb) load_row(tB + e * db, yb, db, vec);
+    if (htg) load_row(tG + i * dg, yg, dg, vec);
+    if (hto) load_row(tO + i * do_, yo, do_, vec);
+    if (om & 1) for (int k = 0; k < da; ++k) ra[k] = (ACC)0;
+    if (om & 2) for (int k = 0; k < db; ++k) rb[k] = (ACC)0;
+    if (om & 4) for (int k = 0; k < dg; ++k) rg[k] = (ACC)0;
+    if (om & 8) for (int k = 0; k < do_; ++k) ro[k] = (ACC)0;
+  }
+  __syncthreads();
+  if (valid && n_ent > 0) {
+    // The rows of one slice never overlap, so the only LDS accesses
+    // that must stay ordered are two updates of one accumulator word.
+    // Entry k's accumulator reads and entry k+1's operand reads are
+    // therefore issued together, ahead of entry k's accumulator
+    // writes: one LDS round trip per entry instead of one per update.
+    int4 q = ent_lds[0];
+    ACC c = (ACC)coef_lds[0];
+    ACC a = xa[q.x], b = xb[q.y], g = xg[q.z], o = xo[q.w];
+    ACC va = hta ? ya[q.x] : (ACC)0, vb = htb ? yb[q.y] : (ACC)0;
+    ACC vg = htg ? yg[q.z] : (ACC)0, vo = hto ? yo[q.w] : (ACC)0;
+    for (int k = 0; k < n_ent; ++k) {
+      const ACC sa = (om & 1) ? ra[q.x] : (ACC)0;
+      const ACC sb = (om & 2) ? rb[q.y] : (ACC)0;
+      const ACC sg = (om & 4) ? rg[q.z] : (ACC)0;
+      const ACC so = (om & 8) ? ro[q.w] : (ACC)0;
+      const int kn = k + 1 < n_ent ? k + 1 : k;
+      const int4 qn = ent_lds[kn];
+      const ACC cn = (ACC)coef_lds[kn];
+      const ACC an = xa[qn.x], bn = xb[qn.y], gn = xg[qn.z],
+                on = xo[qn.w];
+      const ACC van = hta ? ya[qn.x] : (ACC)0;
+      const ACC vbn = htb ? yb[qn.y] : (ACC)0;
+      const ACC vgn = htg ? yg[qn.z] : (ACC)0;
+      const ACC von = hto ? yo[qn.w] : (ACC)0;
+      if (ORDER == 1) {
+        const ACC ab = c * a * b, go = c * g * o;
+        if (om & 1) ra[q.x] = sa + b * go;
+        if (om & 2) rb[q.y] = sb + a * go;
+        if (om & 4) rg[q.z] = sg + ab * o;
+        if (om & 8) ro[q.w] = so + ab * g;
+      } else {
+        // products of a pair and their directional derivatives
+        const ACC ab = c * a * b, dab = c * (va * b + a * vb);
+        const ACC go = c * g * o, dgo = c * (vg * o + g * vo);
+        if (om & 1) ra[q.x] = sa + (vb * go + b * dgo);
+        if (om & 2) rb[q.y] = sb + (va * go + a * dgo);
+        if (om & 4) rg[q.z] = sg + (dab * o + ab * vo);
+        if (om & 8) ro[q.w] = so + (dab * g + ab * vg);
+      }
+      q = qn; c = cn;
+      a = an; b = bn; g = gn; o = on;
+      va = van; vb = vbn; vg = vgn; vo = von;
+    }
+  }
+  if (valid) {
+    if (om & 1) store_row(outA + i * da, ra, da, vec);
+    if (om & 4) store_row(outG + i * dg, rg, dg, vec);
+    if (om & 8) store_row(outO + i * do_, ro, do_, vec);
+  }
+  if (om & 2) {
+    if (nch == 64) {
+      // blockDim is a multiple of 64, so this wave holds row e whole
+      for (int k = 0; k < db; ++k) {
+        ACC v = valid ? rb[k] : (ACC)0;
+        for (int off = 32; off >= 1; off >>= 1)
+          v += __shfl_down(v, off, 64);
+        if ((threadIdx.x & 63) == 0 && valid) outB[e * db + k] = (T)v;
+      }
+    } else if (valid) {
+      for (int k = 0; k < db; ++k) atomicAdd(&outB_acc[e * db + k], rb[k]);
+    }
+  }
+}
+
 }  // namespace
 
 static hipStream_t etp_stream() {
@@ -655,4 +880,154 @@ torch::Tensor etp_reduce(torch::Tensor A, torch::Tensor C, torch::Tensor D,
             idx_ptr(ai), idx_ptr(ci), idx_ptr(di));
       });
   return out.to(A.scalar_type());
+}
+
+// ---- sweep family host side ----------------------------------------
+
+// HYDRAGNN_ETP_SWEEP_VEC=0 keeps element-wise row accesses (A/B aid)
+static bool etp_sweep_vec() {
+  static bool v = []() {
+    const char* e = getenv("HYDRAGNN_ETP_SWEEP_VEC");
+    return !(e && e[0] == '0');
+  }();
+  return v;
+}
+
+static int etp_sweep_block_size() {
+  static int b = []() {
+    const char* e = getenv("HYDRAGNN_ETP_SWEEP_BLOCK");
+    int v = e ? atoi(e) : 128;
+    return (v == 64 || v == 128 || v == 256 || v == 512) ? v : 128;
+  }();
+  return b;
+}
+
+// Dynamic-LDS bytes of one sweep block: block x (input rows + tangent
+// rows + output rows) x accumulator size + staged table.  ops/etp.py
+// asks this before choosing the sweep over single-output kernels.
+long etp_sweep_lds_bytes(long da, long db, long dg, long do_, long n_ent,
+                         long tmask, long omask, long acc_bytes) {
+  SweepLayout L((int)da, (int)db, (int)dg, (int)do_, (int)tmask,
+                (int)omask);
+  size_t slices =
+      ((size_t)etp_sweep_block_size() * L.stride * acc_bytes + 15) &
+      ~(size_t)15;
+  return (long)(slices + (size_t)n_ent * 20);
+}
+
+// Returns {out_a, out_b, out_g, out_o}; slots outside omask come back
+// undefined (None in Python).  order 1 takes no tangents.
+std::vector<torch::Tensor> etp_sweep(
+    torch::Tensor A, torch::Tensor B, torch::Tensor G, torch::Tensor O,
+    c10::optional<torch::Tensor> tA, c10::optional<torch::Tensor> tB,
+    c10::optional<torch::Tensor> tG, c10::optional<torch::Tensor> tO,
+    torch::Tensor entries, torch::Tensor coefs, long omask, long order) {
+  TORCH_CHECK(A.is_cuda() && A.dim() == 3 && B.dim() == 2 &&
+              G.dim() == 3 && O.dim() == 3, "etp_sweep: bad ranks");
+  TORCH_CHECK(order == 1 || order == 2, "etp_sweep: order is 1 or 2");
+  TORCH_CHECK(omask > 0 && omask < 16, "etp_sweep: empty output mask");
+  const long rows = A.size(0);
+  const int nch = A.size(1);
+  const int da = A.size(2), db = B.size(1), dg = G.size(2),
+            do_ = O.size(2);
+  TORCH_CHECK(B.size(0) == rows && G.size(0) == rows &&
+              O.size(0) == rows && G.size(1) == nch && O.size(1) == nch,
+              "etp_sweep: slot shapes disagree");
+  TORCH_CHECK(da <= 192 && db <= 192 && dg <= 192 && do_ <= 192,
+              "etp dims exceed kernel limits");
+  const torch::Tensor* prim[4] = {&A, &B, &G, &O};
+  const c10::optional<torch::Tensor>* tang[4] = {&tA, &tB, &tG, &tO};
+  int tmask = 0;
+  for (int s = 0; s < 4; ++s) {
+    TORCH_CHECK(prim[s]->is_cuda() && prim[s]->is_contiguous() &&
+                prim[s]->scalar_type() == A.scalar_type(),
+                "etp_sweep: primals must be contiguous, one dtype");
+    if (tang[s]->has_value()) {
+      const torch::Tensor& t = **tang[s];
+      TORCH_CHECK(order == 2, "etp_sweep: tangents need order 2");
+      TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == A.scalar_type() &&
+                  t.sizes() == prim[s]->sizes(),
+                  "etp_sweep: tangent must match its primal");
+      tmask |= 1 << s;
+    }
+  }
+  TORCH_CHECK(entries.is_contiguous() && coefs.is_contiguous() &&
+              entries.size(0) == coefs.size(0));
+  const int n_ent = entries.size(0);
+  const bool dbl = A.scalar_type() == at::ScalarType::Double;
+  const bool direct_b = nch == 64;
+
+  std::vector<torch::Tensor> outs(4);
+  if (omask & 1) outs[0] = torch::empty_like(A);
+  if (omask & 4) outs[2] = torch::empty_like(G);
+  if (omask & 8) outs[3] = torch::empty_like(O);
+  torch::Tensor b_acc;
+  if (omask & 2) {
+    if (direct_b) {
+      outs[1] = torch::empty_like(B);
+    } else {
+      b_acc = torch::zeros(
+          {rows, (long)db},
+          A.options().dtype(dbl ? torch::kDouble : torch::kFloat));
+    }
+  }
+  const long NC = rows * nch;
+  if (NC > 0) {
+    const int block = etp_sweep_block_size();
+    const size_t lds_bytes = (size_t)etp_sweep_lds_bytes(
+        da, db, dg, do_, n_ent, tmask, omask, dbl ? 8 : 4);
+    TORCH_CHECK(lds_bytes <= 150 * 1024, "etp_sweep LDS budget exceeded");
+    const long blocks = (NC + block - 1) / block;
+    // packed row accesses need every base on a 16-byte boundary
+    bool vec = etp_sweep_vec();
+    auto aligned = [](const torch::Tensor& t) {
+      return !t.defined() ||
+             reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+    };
+    for (int s = 0; s < 4; ++s) {
+      vec = vec && aligned(*prim[s]) && aligned(outs[s]) &&
+            (!tang[s]->has_value() || aligned(**tang[s]));
+    }
+    AT_DISPATCH_FLOATING_TYPES_AND2(
+        at::ScalarType::BFloat16, at::ScalarType::Half, A.scalar_type(),
+        "etp_sweep", [&] {
+          using ACC = typename acc_of<scalar_t>::type;
+          auto tp = [&](int s) -> const scalar_t* {
+            return tang[s]->has_value()
+                       ? (*tang[s])->data_ptr<scalar_t>() : nullptr;
+          };
+          auto op = [&](int s) -> scalar_t* {
+            return outs[s].defined() ? outs[s].data_ptr<scalar_t>()
+                                     : nullptr;
+          };
+          // compile-time masks for what training launches: edge
+          // products (a,b,g | all four under tangents a,b,g), folds
+          // (a,g | a,g,o under tangents a,g) and etp_reduce (a,g,o)
+          auto kern = order == 1 ? etp_sweep_kernel<scalar_t, 1, -1, -1>
+                                 : etp_sweep_kernel<scalar_t, 2, -1, -1>;
+          if (order == 1 && omask == 7)
+            kern = etp_sweep_kernel<scalar_t, 1, 7, -1>;
+          else if (order == 1 && omask == 5)
+            kern = etp_sweep_kernel<scalar_t, 1, 5, -1>;
+          else if (order == 1 && omask == 13)
+            kern = etp_sweep_kernel<scalar_t, 1, 13, -1>;
+          else if (order == 2 && omask == 15 && tmask == 7)
+            kern = etp_sweep_kernel<scalar_t, 2, 15, 7>;
+          else if (order == 2 && omask == 13 && tmask == 5)
+            kern = etp_sweep_kernel<scalar_t, 2, 13, 5>;
+          hipLaunchKernelGGL(
+              kern, dim3(blocks), dim3(block), lds_bytes, etp_stream(),
+              A.data_ptr<scalar_t>(), B.data_ptr<scalar_t>(),
+              G.data_ptr<scalar_t>(), O.data_ptr<scalar_t>(),
+              tp(0), tp(1), tp(2), tp(3), op(0), op(1),
+              b_acc.defined() ? b_acc.data_ptr<ACC>() : nullptr,
+              op(2), op(3),
+              reinterpret_cast<const int4*>(entries.data_ptr<int>()),
+              coefs.data_ptr<float>(), n_ent, rows, nch, da, db, dg,
+              do_, (int)omask, vec);
+        });
+  }
+  if (b_acc.defined()) outs[1] = b_acc.to(A.scalar_type());
+  return outs;
 }

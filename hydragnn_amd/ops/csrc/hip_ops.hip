@@ -692,6 +692,13 @@ torch::Tensor etp_reduce(torch::Tensor A, torch::Tensor C, torch::Tensor D,
                          c10::optional<torch::Tensor> ai,
                          c10::optional<torch::Tensor> ci,
                          c10::optional<torch::Tensor> di, long n_rows);
+std::vector<torch::Tensor> etp_sweep(
+    torch::Tensor A, torch::Tensor B, torch::Tensor G, torch::Tensor O,
+    c10::optional<torch::Tensor> tA, c10::optional<torch::Tensor> tB,
+    c10::optional<torch::Tensor> tG, c10::optional<torch::Tensor> tO,
+    torch::Tensor entries, torch::Tensor coefs, long omask, long order);
+long etp_sweep_lds_bytes(long da, long db, long dg, long do_, long n_ent,
+                         long tmask, long omask, long acc_bytes);
 
 // defined in varlen_attn.hip
 torch::Tensor varlen_attention(torch::Tensor Q, torch::Tensor K,
@@ -757,6 +764,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("ci") = pybind11::none(),
         pybind11::arg("di") = pybind11::none(),
         pybind11::arg("n_rows") = 0);
+  m.def("etp_sweep", &etp_sweep,
+        "several derivatives of the ETP form in one launch (HIP)",
+        pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("G"),
+        pybind11::arg("O"), pybind11::arg("tA") = pybind11::none(),
+        pybind11::arg("tB") = pybind11::none(),
+        pybind11::arg("tG") = pybind11::none(),
+        pybind11::arg("tO") = pybind11::none(),
+        pybind11::arg("entries"), pybind11::arg("coefs"),
+        pybind11::arg("omask"), pybind11::arg("order") = 1);
+  m.def("etp_sweep_lds_bytes", &etp_sweep_lds_bytes,
+        "dynamic-LDS bytes of one etp_sweep block");
   m.def("gather_fwd", &gather_fwd, "gather rows (HIP)");
   m.def("scatter_sum_fwd", &scatter_sum_fwd, "scatter-add (HIP)");
   m.def("segment_sum_csr", &segment_sum_csr, "CSR segment sum (HIP)",

@@ -8,12 +8,15 @@ weights), its gradients, and the symmetric-contraction fold steps.
 Key property: gradients of a trilinear form are trilinear forms with
 role-permuted tables, and the channel-reduced B-gradient closes the
 family.  So both autograd passes of force training (create_graph=True)
-run on the two fused HIP kernels (csrc/etp.hip); CPU and fp64 use a
-dense-einsum path that autograd differentiates directly.
+run on the fused HIP kernels (csrc/etp.hip); CPU uses a dense-einsum
+path that autograd differentiates directly.  The backward passes run
+as sweeps: one launch yields every wanted first derivative, and one
+more the whole second-order contribution (see "Sweep family" below).
 """
 
 from __future__ import annotations
 
+import os
 from typing import Dict, Tuple
 
 import torch
@@ -109,6 +112,187 @@ def _kernel_ok(table: ETPTable, *tensors) -> bool:
             and not use_eager())
 
 
+# ---------------------------------------------------------------------------
+# Sweep family.  The contraction is one quadrilinear form
+#   Q(a, b, g, o) = sum_k coef_k a[a_k] b[b_k] g[g_k] o[o_k]
+# (a, g, o: [rows, nch, d]; b: [rows, db]) and every kernel above is
+# dQ/dslot.  A sweep produces several of these derivatives in one walk
+# of the entry table with every row staged once (csrc/etp.hip,
+# etp_sweep_kernel), instead of one single-output launch per derivative
+# plus the adds that sum second-order contributions.
+# ---------------------------------------------------------------------------
+_SLOTS = "abgo"
+_SLOT_SUB = {"a": "eca", "b": "eb", "g": "ecg", "o": "eco"}
+_LDS_BUDGET = 150 * 1024
+
+# how often each path ran (tests read this to see a fallback happen)
+sweep_stats = {"sweep1": 0, "sweep2": 0, "compose1": 0, "compose2": 0}
+
+
+def _sweep_mode() -> int:
+    """HYDRAGNN_ETP_SWEEP: 0 = single-output kernels only, 1 = fused
+    first-order backward, 2 = fused first- and second-order (default)."""
+    v = os.environ.get("HYDRAGNN_ETP_SWEEP", "2")
+    return int(v) if v in ("0", "1", "2") else 2
+
+
+def _dense_dq(slots, s: int, W):
+    """dQ/dslot_s as a dense einsum over the other three slots."""
+    others = [r for r in range(4) if r != s]
+    expr = ",".join(_SLOT_SUB[_SLOTS[r]] for r in others) + \
+        ",abgo->" + _SLOT_SUB[_SLOTS[s]]
+    return torch.einsum(expr, *[slots[r] for r in others], W)
+
+
+def _dense_sweep(primals, tangents, mask, table: ETPTable):
+    """Pure-torch reference of the sweep kernels.
+
+    primals: (a, b, g, o) slot tensors.  mask: four bools, the wanted
+    output slots.  tangents None -> first order: out_s = dQ/ds.
+    Otherwise a 4-tuple with None for absent tangents -> second order:
+    out_s = sum over r != s with t_r present of dQ/ds with slot r
+    replaced by t_r.  Returns a 4-tuple, None outside the mask (and for
+    a second-order slot that no present tangent reaches)."""
+    W = table.dense(primals[0].device, torch.float32).to(primals[0].dtype)
+    outs = []
+    for s in range(4):
+        if not mask[s]:
+            outs.append(None)
+        elif tangents is None:
+            outs.append(_dense_dq(primals, s, W))
+        else:
+            acc = None
+            for r in range(4):
+                if r == s or tangents[r] is None:
+                    continue
+                slots = list(primals)
+                slots[r] = tangents[r]
+                term = _dense_dq(slots, s, W)
+                acc = term if acc is None else acc + term
+            outs.append(acc)
+    return tuple(outs)
+
+
+def _single_dq(slots, s: int, table: ETPTable):
+    """dQ/dslot_s through the single-output kernels."""
+    a, b, g, o = slots
+    if s == 0:
+        return etp_general(o, b, g, table.perm("obga"))
+    if s == 1:
+        return etp_reduce(a, g, o, table)
+    if s == 2:
+        return etp_general(a, b, o, table.perm("abog"))
+    return etp_general(a, b, g, table)
+
+
+def _compose_second(primals, tangents, mask, table: ETPTable):
+    """Second-order sweep as single-output launches plus adds."""
+    outs = []
+    for s in range(4):
+        acc = None
+        if mask[s]:
+            for r in range(4):
+                if r == s or tangents[r] is None:
+                    continue
+                slots = list(primals)
+                slots[r] = tangents[r]
+                term = _single_dq(slots, s, table)
+                acc = term if acc is None else acc + term
+        outs.append(acc)
+    return tuple(outs)
+
+
+def _bits(flags) -> int:
+    return sum(1 << s for s in range(4) if flags[s])
+
+
+def _sweep_fits(table: ETPTable, primals, tangents, mask) -> bool:
+    """Kernel dtype/device conditions plus the sweep's own LDS
+    footprint: block x (input + tangent + output rows) x accumulator
+    size + table, against the family's 150 KiB budget."""
+    if not _kernel_ok(table, *primals):
+        return False
+    tmask = 0 if tangents is None else _bits(
+        [t is not None for t in tangents])
+    acc = 8 if primals[0].dtype == torch.float64 else 4
+    da, db, dg, do = table.dims
+    ext = get_extension(required=True)
+    return ext.etp_sweep_lds_bytes(
+        da, db, dg, do, table.entries.shape[0], tmask, _bits(mask),
+        acc) <= _LDS_BUDGET
+
+
+def etp_sweep(primals, tangents, mask, table: ETPTable):
+    """Sweep on the HIP kernel where it applies, `_dense_sweep`
+    elsewhere (CPU, forced eager, unsupported dtypes, over budget).
+    Not differentiable by itself: `_ETPSweep1` carries the autograd."""
+    primals = tuple(primals)
+    assert tuple(primals[0].shape[2:]) == (table.dims[0],) and \
+        primals[1].shape[1] == table.dims[1] and \
+        primals[2].shape[2] == table.dims[2] and \
+        primals[3].shape[2] == table.dims[3], "slot dims vs table"
+    if tangents is not None:
+        tangents = tuple(tangents)
+        # a slot reached by no present tangent is identically zero
+        mask = tuple(bool(mask[s]) and any(
+            tangents[r] is not None for r in range(4) if r != s)
+            for s in range(4))
+    if not any(mask):
+        return (None, None, None, None)
+    if not _sweep_fits(table, primals, tangents, mask):
+        return _dense_sweep(primals, tangents, mask, table)
+    ext = get_extension(required=True)
+    ent, coefs, _ = table.device_tensors(primals[0].device)
+    tang = [None] * 4 if tangents is None else [
+        None if t is None else t.contiguous() for t in tangents]
+    outs = ext.etp_sweep(*[p.contiguous() for p in primals], *tang,
+                         ent, coefs, _bits(mask),
+                         1 if tangents is None else 2)
+    return tuple(outs)
+
+
+class _ETPSweep1(torch.autograd.Function):
+    """(a, b, g, o) -> (dQ/da, dQ/db, dQ/dg, dQ/do) on the masked
+    slots (None elsewhere), one launch.  Its backward is the
+    second-order sweep with the incoming cotangents as tangents."""
+
+    @staticmethod
+    def forward(ctx, a, b, g, o, table, mask):
+        ctx.save_for_backward(a, b, g, o)
+        ctx.table = table
+        ctx.set_materialize_grads(False)
+        sweep_stats["sweep1"] += 1
+        return etp_sweep((a, b, g, o), None, mask, table)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *tangents):
+        primals = ctx.saved_tensors
+        table = ctx.table
+        mask = tuple(ctx.needs_input_grad[:4])
+        if _kernel_ok(table, *primals) and not (
+                _sweep_mode() >= 2
+                and _sweep_fits(table, primals, tangents, mask)):
+            # first-order-only mode, or over the LDS budget
+            sweep_stats["compose2"] += 1
+            outs = _compose_second(primals, tangents, mask, table)
+        else:
+            sweep_stats["sweep2"] += 1
+            outs = etp_sweep(primals, tangents, mask, table)
+        return outs + (None, None)
+
+
+def _first_order(primals, mask, table: ETPTable):
+    """Masked first derivatives of Q: one sweep launch when enabled and
+    within the LDS budget, else None (caller composes single-output
+    kernels, as before the sweep family)."""
+    if _sweep_mode() >= 1 and any(mask) and \
+            _sweep_fits(table, primals, None, mask):
+        return _ETPSweep1.apply(*primals, table, tuple(mask))
+    sweep_stats["compose1"] += 1
+    return None
+
+
 class _ETPGeneral(torch.autograd.Function):
     @staticmethod
     def forward(ctx, A, B, C, table):
@@ -125,6 +309,10 @@ class _ETPGeneral(torch.autograd.Function):
         A, B, C = ctx.saved_tensors
         table = ctx.table
         gout = gout.contiguous()
+        mask = tuple(ctx.needs_input_grad[:3]) + (False,)
+        swept = _first_order((A, B, C, gout), mask, table)
+        if swept is not None:
+            return swept[0], swept[1], swept[2], None
         gA = gB = gC = None
         if ctx.needs_input_grad[0]:
             gA = etp_general(gout, B, C, table.perm("obga"))
@@ -152,6 +340,12 @@ class _ETPReduce(torch.autograd.Function):
         A, C, D = ctx.saved_tensors
         table = ctx.table
         gout = gout.contiguous()
+        need = ctx.needs_input_grad
+        # gout sits in the b slot: the three outputs share their inputs
+        swept = _first_order((A, gout, C, D),
+                             (need[0], False, need[1], need[2]), table)
+        if swept is not None:
+            return swept[0], swept[2], swept[3], None
         gA = gC = gD = None
         if ctx.needs_input_grad[0]:
             # gA[e,c,a] = sum coef gout[b] C[g] D[o]

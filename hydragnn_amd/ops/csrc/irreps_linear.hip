@@ -31,6 +31,18 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int BM = 32;       // n rows per workgroup
 constexpr int MAXD = 16;     // (lmax+1)^2, lmax <= 3
 constexpr int PAD = 8;       // bf16 elems of row padding (16 B)
+// LDS per workgroup: the dynamic staging buffers plus each kernel's
+// static lmap_s table
+constexpr size_t LDS_BUDGET = 160 * 1024;
+constexpr size_t LDS_STATIC = MAXD * sizeof(int);
+
+// A refused launch (e.g. LDS over the limit) must not hand back the
+// uninitialised output.
+inline void check_launch(const char* what) {
+  hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, what, " launch failed: ",
+              hipGetErrorString(err));
+}
 
 template <bool TRANS_W>
 __global__ __launch_bounds__(256) void irreps_linear_kernel(
@@ -273,7 +285,8 @@ torch::Tensor irreps_linear(torch::Tensor X, torch::Tensor W,
   TORCH_CHECK(D <= 16 && lmap.numel() == D);
   size_t lds_bytes = ((size_t)D * BM * (Cin + 8) +
                       (size_t)L * Cin * (Cout + 8)) * 2;
-  TORCH_CHECK(lds_bytes <= 160 * 1024, "irreps_linear LDS budget");
+  TORCH_CHECK(lds_bytes + LDS_STATIC <= LDS_BUDGET,
+              "irreps_linear LDS budget");
   auto out = torch::empty({N, (long)Cout, (long)D}, X.options());
   if (N == 0) return out;
   const float* bias_ptr = nullptr;
@@ -304,6 +317,7 @@ torch::Tensor irreps_linear(torch::Tensor X, torch::Tensor W,
   };
   if (trans_w) launch(irreps_linear_kernel<true>);
   else launch(irreps_linear_kernel<false>);
+  check_launch("irreps_linear");
   return out;
 }
 
@@ -324,7 +338,8 @@ torch::Tensor irreps_linear_gw(torch::Tensor X, torch::Tensor G,
               "irreps_linear_gw shape envelope");
   size_t lds_bytes = ((size_t)D * BM * (Cin + 8) +
                       (size_t)D * BM * (Cout + 8)) * 2;
-  TORCH_CHECK(lds_bytes <= 160 * 1024, "irreps_linear_gw LDS budget");
+  TORCH_CHECK(lds_bytes + LDS_STATIC <= LDS_BUDGET,
+              "irreps_linear_gw LDS budget");
   auto partials = torch::empty(
       {nblocks, L, Cin, Cout},
       X.options().dtype(torch::kFloat));
@@ -337,6 +352,7 @@ torch::Tensor irreps_linear_gw(torch::Tensor X, torch::Tensor G,
                      reinterpret_cast<const __hip_bfloat16*>(G.data_ptr()),
                      partials.data_ptr<float>(),
                      lmap_c.data_ptr<long>(), N, Cin, Cout, D, (int)L);
+  check_launch("irreps_linear_gw");
   return partials;
 }
 

@@ -19,6 +19,11 @@ than the torch path end-to-end (permuted copies of x and g); the
 kernel version flips the A/B to +1.3% (32.7k vs 32.3k g/s, default
 bench).  First and second order both stay on the kernels, so force
 training works.
+
+Eligibility is decided on the forward shape only, so every backward
+route checks the host envelope of the kernel it would enter for the
+shape that kernel will see (gX swaps the channels, gW has its own LDS
+footprint) and otherwise runs the differentiable torch composition.
 """
 
 from __future__ import annotations
@@ -27,15 +32,54 @@ import torch
 
 from ._extension import get_extension, use_eager
 
-_MAX_LDS = 160 * 1024
+# host envelopes of the two entry points (csrc/irreps_linear.hip): the
+# dynamic LDS plus the kernels' static 64 B lmap table must fit 160 KiB
+_MAX_LDS = 160 * 1024 - 64
+_BM = 32
+
+
+def irreps_fwd_kernel_ok(c_in: int, c_out: int, d: int,
+                         n_l: int) -> bool:
+    """Host envelope of `irreps_linear` (either trans_w) for a
+    [*, c_in, d] input mixed to c_out channels."""
+    if c_in % 32 != 0 or c_out % 64 != 0 or d > 16:
+        return False
+    lds = (d * _BM * (c_in + 8) + n_l * c_in * (c_out + 8)) * 2
+    return lds <= _MAX_LDS
+
+
+def irreps_gw_kernel_ok(c_in: int, c_out: int, d: int,
+                        n_l: int) -> bool:
+    """Host envelope of `irreps_linear_gw` for x [*, c_in, d] and
+    g [*, c_out, d]."""
+    tiles = (c_in // 16) * (c_out // 16)
+    if (c_in % 16 != 0 or c_out % 16 != 0 or tiles % 4 != 0
+            or tiles > 16 or n_l > 4 or d > 16):
+        return False
+    lds = (d * _BM * (c_in + 8) + d * _BM * (c_out + 8)) * 2
+    return lds <= _MAX_LDS
 
 
 def irreps_kernel_ok(n: int, c_in: int, c_out: int, d: int,
                      n_l: int) -> bool:
-    if c_in % 32 != 0 or c_out % 64 != 0 or d > 16:
-        return False
-    lds = (d * 32 * (c_in + 8) + n_l * c_in * (c_out + 8)) * 2
-    return lds <= _MAX_LDS and n >= 64
+    return irreps_fwd_kernel_ok(c_in, c_out, d, n_l) and n >= 64
+
+
+def _mix(x, W, lmap, trans_w):
+    """The forward map (no bias/residual) as differentiable torch ops:
+    one batched GEMM over the D slices."""
+    Wk = W.transpose(1, 2) if trans_w else W
+    return torch.bmm(x.permute(2, 0, 1),
+                     Wk[lmap]).permute(1, 2, 0).contiguous()
+
+
+def _mix_routed(x, W, lmap, trans_w):
+    """`_mix` on the kernel when the shape THIS call sees is inside the
+    host envelope, else the torch composition."""
+    c_out = W.shape[1] if trans_w else W.shape[2]
+    if irreps_fwd_kernel_ok(x.shape[1], c_out, x.shape[2], W.shape[0]):
+        return _IrrepsLinearFn.apply(x, W, lmap, None, trans_w)
+    return _mix(x, W, lmap, trans_w)
 
 
 class _IrrepsLinearFn(torch.autograd.Function):
@@ -60,30 +104,56 @@ class _IrrepsLinearFn(torch.autograd.Function):
         ga = g if (len(ctx.needs_input_grad) > 5
                    and ctx.needs_input_grad[5]) else None
         if ctx.needs_input_grad[0]:
-            gx = _IrrepsLinearFn.apply(g, W, lmap, None, not trans_w)
+            # same kernel, channels swapped: its envelope is checked
+            # for the swapped shape
+            gx = _mix_routed(g, W, lmap, not trans_w)
         if ctx.needs_input_grad[1]:
-            cin, cout = x.shape[1], g.shape[1]
-            tiles = (cin // 16) * (cout // 16)
-            if (cin % 16 == 0 and cout % 16 == 0 and tiles % 4 == 0
-                    and tiles <= 16 and W.shape[0] <= 4):
-                # copy-free MFMA contraction over n: per-block fp32
-                # partials (deterministic), summed here
-                ext = get_extension(required=True)
-                nblocks = min(512, (x.shape[0] + 31) // 32)
-                parts = ext.irreps_linear_gw(x.contiguous(), g, lmap,
-                                             W.shape[0], nblocks)
-                gw = parts.sum(0)
-            else:
-                # fallback: per-m batched GEMM + fold m -> l
-                gw_m = torch.bmm(x.permute(2, 1, 0), g.permute(2, 0, 1))
-                gw = gw_m.new_zeros(W.shape[0], cin, cout)
-                gw.index_add_(0, lmap, gw_m)
+            gw = _weight_grad(x, g, lmap, W.shape[0])
             if trans_w:
                 gw = gw.transpose(1, 2)
             gw = gw.to(W.dtype)
         if bias is not None and ctx.needs_input_grad[3]:
             gb = g[:, :, 0].sum(0).to(bias.dtype)
         return gx, gw, None, gb, None, ga
+
+
+class _IrrepsGWFn(torch.autograd.Function):
+    """gW[l,i,o] = sum_{n, m in l} x[n,i,m] * g[n,o,m] in fp32 on the
+    copy-free MFMA contraction over n: per-block fp32 partials
+    (deterministic), summed here.  Bilinear in (x, g), so both
+    gradients are the forward map again with the cotangent as weight."""
+
+    @staticmethod
+    def forward(ctx, x, g, lmap, n_l):
+        ext = get_extension(required=True)
+        nblocks = min(512, (x.shape[0] + _BM - 1) // _BM)
+        parts = ext.irreps_linear_gw(x.contiguous(), g.contiguous(),
+                                     lmap, n_l, nblocks)
+        ctx.save_for_backward(x, g, lmap)
+        return parts.sum(0)
+
+    @staticmethod
+    def backward(ctx, h):
+        x, g, lmap = ctx.saved_tensors
+        h = h.to(x.dtype).contiguous()
+        gx = gg = None
+        if ctx.needs_input_grad[0]:
+            gx = _mix_routed(g, h, lmap, True)
+        if ctx.needs_input_grad[1]:
+            gg = _mix_routed(x, h, lmap, False)
+        return gx, gg, None, None
+
+
+def _weight_grad(x, g, lmap, n_l):
+    """[n_l, c_in, c_out] weight gradient: the gW kernel (fp32) inside
+    its host envelope, else a per-m batched GEMM folded m -> l."""
+    c_in, c_out = x.shape[1], g.shape[1]
+    if irreps_gw_kernel_ok(c_in, c_out, x.shape[2], n_l):
+        return _IrrepsGWFn.apply(x, g, lmap, n_l)
+    gw_m = torch.bmm(x.permute(2, 1, 0), g.permute(2, 0, 1))
+    gw = gw_m.new_zeros(n_l, c_in, c_out)
+    gw.index_add_(0, lmap, gw_m)
+    return gw
 
 
 def irreps_linear(x: torch.Tensor, W: torch.Tensor, lmap: torch.Tensor,

@@ -78,27 +78,27 @@ class _MFMAMatmul(torch.autograd.Function):
 
 
 class _MFMALinearFn(torch.autograd.Function):
+    """bf16 x @ weight^T + bias.  Takes bf16 operands and saves them:
+    the casts live in `mfma_linear_bf16`, outside the Function, so
+    autograd owns them and the double backward reaches fp32 leaves."""
+
     @staticmethod
     def forward(ctx, x, weight, bias):
-        xb = x.to(torch.bfloat16).contiguous()
-        wb = weight.to(torch.bfloat16).contiguous()
-        ctx.save_for_backward(xb, wb)
+        ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
-        ctx.w_dtype = weight.dtype
-        ctx.x_dtype = x.dtype
         ext = get_extension(required=True)
-        return ext.mfma_linear(xb, wb,
+        return ext.mfma_linear(x, weight,
                                bias if bias is not None else None, True)
 
     @staticmethod
     def backward(ctx, g):
-        xb, wb = ctx.saved_tensors
+        x, weight = ctx.saved_tensors
         g = g.contiguous().to(torch.bfloat16)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = _MFMAMatmul.apply(g, wb, False).to(ctx.x_dtype)
+            gx = _MFMAMatmul.apply(g, weight, False)
         if ctx.needs_input_grad[1]:
-            gw = _splitk_weight_grad(xb, g, 64).to(ctx.w_dtype)
+            gw = _splitk_weight_grad(x, g, 64)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = g.float().sum(0)
         return gx, gw, gb
@@ -108,43 +108,55 @@ class _GemvLinearFn(torch.autograd.Function):
     """Linear with out_features <= 8: forward on the gemv_small_n
     kernel (hipBLASLt runs N=1 on MT1x4x256 tiles ~30x off roofline);
     backward composed of differentiable ops so the force-training
-    double backward works unchanged."""
+    double backward works unchanged.  bf16 operands, cast by
+    `gemv_linear_bf16`."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        xb = x.to(torch.bfloat16).contiguous()
-        wb = weight.to(torch.bfloat16).contiguous()
-        ctx.save_for_backward(xb, wb)
+        ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
-        ctx.w_dtype = weight.dtype
-        ctx.x_dtype = x.dtype
         ext = get_extension(required=True)
-        return ext.gemv_small_n(xb, wb,
+        return ext.gemv_small_n(x, weight,
                                 bias if bias is not None else None)
 
     @staticmethod
     def backward(ctx, g):
-        xb, wb = ctx.saved_tensors
+        x, weight = ctx.saved_tensors
         g = g.contiguous().to(torch.bfloat16)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            if wb.shape[0] == 1:
-                gx = (g * wb.reshape(-1)).to(ctx.x_dtype)
+            if weight.shape[0] == 1:
+                gx = g * weight.reshape(-1)
             else:
-                gx = (g @ wb).to(ctx.x_dtype)
+                gx = g @ weight
         if ctx.needs_input_grad[1]:
-            if wb.shape[0] == 1:
+            if weight.shape[0] == 1:
                 # dW[0,k] = sum_m g[m,0] x[m,k]: a weighted column sum
                 # (the split-K bmm here is a degenerate M=1 batched
                 # GEMM that hipBLASLt runs on MT1x4 tiles ~50x off
                 # roofline)
-                gw = (xb.float() * g.float()).sum(0, keepdim=True) \
-                    .to(ctx.w_dtype)
+                gw = (x.float() * g.float()).sum(0, keepdim=True) \
+                    .to(torch.bfloat16)
             else:
-                gw = _splitk_weight_grad(xb, g, 64).to(ctx.w_dtype)
+                gw = _splitk_weight_grad(x, g, 64)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = g.float().sum(0)
         return gx, gw, gb
+
+
+def mfma_linear_bf16(x, weight, bias):
+    """x @ weight^T + bias on the MFMA kernel.  fp32 operands (the
+    autocast case) are cast here, as differentiable ops."""
+    return _MFMALinearFn.apply(x.to(torch.bfloat16).contiguous(),
+                               weight.to(torch.bfloat16).contiguous(),
+                               bias)
+
+
+def gemv_linear_bf16(x, weight, bias):
+    """As `mfma_linear_bf16`, on the narrow-output GEMV kernel."""
+    return _GemvLinearFn.apply(x.to(torch.bfloat16).contiguous(),
+                               weight.to(torch.bfloat16).contiguous(),
+                               bias)
 
 
 class MFMALinear(SplitKLinear):
@@ -159,8 +171,8 @@ class MFMALinear(SplitKLinear):
             and x.dim() == 2)
         if hip_ok and _eligible(x.shape[0], self.out_features,
                                 self.in_features):
-            return _MFMALinearFn.apply(x, self.weight, self.bias)
+            return mfma_linear_bf16(x, self.weight, self.bias)
         if (hip_ok and self.out_features <= 8
                 and self.in_features % 8 == 0 and x.shape[0] >= 256):
-            return _GemvLinearFn.apply(x, self.weight, self.bias)
+            return gemv_linear_bf16(x, self.weight, self.bias)
         return super().forward(x)

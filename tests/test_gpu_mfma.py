@@ -48,6 +48,11 @@ def test_mfma_matmul_bias():
     out = ext.mfma_linear(A, B, bias, True)
     ref = A.float() @ B.t().float() + bias
     assert (out.float() - ref).abs().max() < 0.15 * ref.abs().max()
+    # that bound is wider than max|bias|: a dropped bias must not pass
+    # (bit-exact bias cases: test_gpu_linear_exact.py)
+    err = (out.float() - ref).abs()
+    err_nobias = (out.float() - (ref - bias)).abs()
+    assert err.max() < err_nobias.max()
 
 
 def test_mfma_linear_grads_match_reference():

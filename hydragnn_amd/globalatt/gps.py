@@ -6,11 +6,12 @@ MultiheadAttention or Performer/FAVOR+ linear attention) + MLP, with
 residuals and three norms; Performer projection redraw is driven by the
 training loop, not forward (safe under activation checkpointing).
 
-On MI355X the multihead path runs the segment-varlen HIP kernel
-(ops/csrc/varlen_attn.hip): one (graph, head) workgroup with K/V in
-LDS and an online softmax over exactly the graph's nodes — no dense
-padding.  Batches outside its envelope (head_dim > 32 or a graph with
-> 256 nodes) and the Performer path fall back to dense-batch SDPA.
+On MI355X the multihead path runs the segment-varlen HIP kernels
+(ops/csrc/varlen_attn.hip), forward and first-order backward: one
+(graph, head) workgroup with the other side tiled through LDS, over
+exactly the graph's nodes — no dense padding, fp32 or bf16, graphs of
+any size.  Heads wider than 128 and the Performer path fall back to
+dense-batch SDPA.
 """
 
 from __future__ import annotations
@@ -126,8 +127,9 @@ class HydraGPSConv(nn.Module):
 
     def _try_varlen_attention(self, x, batch):
         """Run nn.MultiheadAttention's math through the segment-varlen
-        HIP kernel (no dense padding).  Returns None when the batch
-        does not fit the kernel envelope (falls back to dense SDPA)."""
+        HIP kernels (no dense padding).  Returns None outside their
+        envelope (head_dim > 128, no GPU, or HYDRAGNN_VARLEN_ATTN=0);
+        the caller then falls back to dense SDPA."""
         from ..ops.scatter import _rowptr_from_sorted
         from ..ops.varlen_attn import varlen_attention, varlen_eligible
         attn = self.attn

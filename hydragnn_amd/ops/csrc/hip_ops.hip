@@ -703,6 +703,14 @@ long etp_sweep_lds_bytes(long da, long db, long dg, long do_, long n_ent,
 // defined in varlen_attn.hip
 torch::Tensor varlen_attention(torch::Tensor Q, torch::Tensor K,
                                torch::Tensor V, torch::Tensor ptr);
+std::vector<torch::Tensor> varlen_attention_fwd(
+    torch::Tensor Q, torch::Tensor K, torch::Tensor V,
+    torch::Tensor ptr);
+std::vector<torch::Tensor> varlen_attention_bwd(
+    torch::Tensor Q, torch::Tensor K, torch::Tensor V, torch::Tensor O,
+    torch::Tensor LSE, torch::Tensor dO, torch::Tensor ptr);
+long varlen_attention_lds_bytes(long dh, long pass);
+std::vector<long> varlen_attention_tiling(long dh);
 
 // defined in irreps_linear.hip
 torch::Tensor irreps_linear(torch::Tensor X, torch::Tensor W,
@@ -797,6 +805,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("shifts") = pybind11::none());
   m.def("varlen_attention", &varlen_attention,
         "segment-varlen attention (HIP)");
+  m.def("varlen_attention_fwd", &varlen_attention_fwd,
+        "segment-varlen attention forward -> (O, LSE) (HIP)");
+  m.def("varlen_attention_bwd", &varlen_attention_bwd,
+        "segment-varlen attention backward -> (dQ, dK, dV) (HIP)");
+  m.def("varlen_attention_lds_bytes", &varlen_attention_lds_bytes,
+        "LDS bytes of a varlen-attention instance "
+        "(pass 0 fwd, 1 dQ, 2 dK/dV)",
+        pybind11::arg("dh"), pybind11::arg("pass"));
+  m.def("varlen_attention_tiling", &varlen_attention_tiling,
+        "(tile rows, rows per workgroup pass) of the instance for dh");
   m.def("irreps_linear", &irreps_linear,
         "per-l channel-mixing MFMA linear (HIP)",
         pybind11::arg("X"), pybind11::arg("W"), pybind11::arg("lmap"),

@@ -10,9 +10,17 @@
 // required seg <= 256 and fp32 only).
 //
 // dtype: fp32 or bf16 inputs; LDS staging and accumulation in fp32.
-// head_dim <= 64.  Backward is recompute-based on the Python side
-// (torch ops), keeping double-backward support without a
-// hand-written second-order kernel.
+//
+// Two kernel generations live here:
+//  * varlen_attn_kernel (head_dim <= 64): the original forward entry
+//    point, per-thread rows as runtime-indexed LDS slices.
+//  * varlen_attn_fwd_kernel / _dq_kernel / _dkv_kernel (head_dim <=
+//    128): the training path.  Templated on a compile-time per-lane
+//    width so the thread's own rows live in registers; the forward
+//    also stores the row log-sum-exp, and the backward is two
+//    atomic-free passes (thread = query row for dQ, thread = key row
+//    for dK/dV) that recompute P from LSE.  The double backward stays
+//    on torch ops on the Python side.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -114,7 +122,474 @@ __global__ __launch_bounds__(kThreads) void varlen_attn_kernel(
   }
 }
 
+// ---------------------------------------------------------------
+// Training path: forward with LSE, and the two backward passes.
+//
+// An instance is VCfg<DHL, L, T>: every row (query or key) is owned by
+// L adjacent lanes, each holding DHL consecutive head dims of it in
+// registers (compile-time unrolled; dims past the runtime head_dim are
+// zero, in registers and in the LDS tiles alike, so no inner loop
+// carries a bound check).  L = 2 covers 64 < head_dim <= 128 with 64
+// registers per row per lane; the two partial dot products meet in
+// one __shfl_xor, a fixed order, so results stay bitwise reproducible.
+// The other side is staged through LDS in T-row fp32 tiles.  All lanes
+// read the same tile row (a broadcast); with L = 2 the two lane
+// halves of a row are kSub = DHL + 4 floats apart, which puts their
+// 16-byte reads on different banks (DHL alone would be 64 dwords = the
+// same bank) and keeps them 16-byte aligned.
+
+constexpr int kBlock = 128;            // threads per workgroup
+constexpr long kLdsBudget = 160 * 1024;
+
+template <int DHL_, int L_, int T_>
+struct VCfg {
+  static constexpr int DHL = DHL_;     // head dims per lane
+  static constexpr int L = L_;         // lanes per row
+  static constexpr int T = T_;         // tile rows per LDS pass
+  static constexpr int kRows = kBlock / L;   // rows owned per pass
+  static constexpr int kCap = L * DHL;       // head_dim ceiling
+  static constexpr int kSub = DHL + (L > 1 ? 4 : 0);
+  static constexpr int kRowStride = L * kSub;
+  static constexpr int kTileFloats = T * kRowStride;
+  // static LDS bytes per pass (no dynamic LDS): two tiles; the dK/dV
+  // pass also stages LSE and D of the tile's query rows
+  static constexpr long kLdsFwd = 2L * kTileFloats * sizeof(float);
+  static constexpr long kLdsDq = kLdsFwd;
+  static constexpr long kLdsDkv = kLdsFwd + 2L * T * sizeof(float);
+};
+
+using VCfg16 = VCfg<16, 1, 64>;
+using VCfg32 = VCfg<32, 1, 64>;
+using VCfg64 = VCfg<64, 1, 64>;
+using VCfg128 = VCfg<64, 2, 32>;
+
+// Stage tn rows of one head into an LDS tile, zero past head_dim.
+// src points at (first row, head h); rows are rs elements apart.
+template <typename C, typename T>
+__device__ inline void stage_tile(float* __restrict__ dst,
+                                  const T* __restrict__ src, long rs,
+                                  int tn, int dh) {
+  for (int i = threadIdx.x; i < tn * C::kCap; i += kBlock) {
+    int row = i / C::kCap, d = i % C::kCap;
+    float x = d < dh ? to_f32<T>(src[row * rs + d]) : 0.f;
+    dst[row * C::kRowStride + (d / C::DHL) * C::kSub + d % C::DHL] = x;
+  }
+}
+
+// This lane's DHL dims of a row into registers (times mul), zero
+// where the row or the dim does not exist.
+template <typename C, typename T>
+__device__ inline void load_row(float (&r)[C::DHL],
+                                const T* __restrict__ p, int sub, int dh,
+                                bool on, float mul) {
+#pragma unroll
+  for (int d = 0; d < C::DHL; ++d) {
+    int c = sub * C::DHL + d;
+    r[d] = (on && c < dh) ? to_f32<T>(p[c]) * mul : 0.f;
+  }
+}
+
+template <typename C, typename T>
+__device__ inline void store_row(T* __restrict__ p,
+                                 const float (&r)[C::DHL], int sub,
+                                 int dh, float mul) {
+#pragma unroll
+  for (int d = 0; d < C::DHL; ++d) {
+    int c = sub * C::DHL + d;
+    if (c < dh) p[c] = from_f32<T>(r[d] * mul);
+  }
+}
+
+// Register row times one lane-slice of an LDS tile row, summed over
+// the row's L lanes.
+template <typename C>
+__device__ inline float dot_row(const float (&a)[C::DHL],
+                                const float* __restrict__ b) {
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+  for (int d = 0; d < C::DHL; d += 4) {
+    float4 x = *reinterpret_cast<const float4*>(b + d);
+    s0 += a[d] * x.x;
+    s1 += a[d + 1] * x.y;
+    s2 += a[d + 2] * x.z;
+    s3 += a[d + 3] * x.w;
+  }
+  float s = (s0 + s1) + (s2 + s3);
+  if (C::L > 1) s += __shfl_xor(s, 1);
+  return s;
+}
+
+template <typename C>
+__device__ inline void axpy_row(float (&acc)[C::DHL], float a,
+                                const float* __restrict__ b) {
+#pragma unroll
+  for (int d = 0; d < C::DHL; d += 4) {
+    float4 x = *reinterpret_cast<const float4*>(b + d);
+    acc[d] += a * x.x;
+    acc[d + 1] += a * x.y;
+    acc[d + 2] += a * x.z;
+    acc[d + 3] += a * x.w;
+  }
+}
+
+// Forward, thread = query row, K/V tiled; also writes LSE = m + log l.
+template <typename C, typename T>
+__global__ __launch_bounds__(kBlock) void varlen_attn_fwd_kernel(
+    const T* __restrict__ Q,   // [N, H, dh]
+    const T* __restrict__ K, const T* __restrict__ V,
+    T* __restrict__ O,         // [N, H, dh]
+    float* __restrict__ LSE,   // [N, H]
+    const long* __restrict__ ptr, int H, int dh, float scale) {
+  __shared__ __align__(16) float lK[C::kTileFloats];
+  __shared__ __align__(16) float lV[C::kTileFloats];
+
+  const int h = blockIdx.y;
+  const long lo = ptr[blockIdx.x], hi = ptr[blockIdx.x + 1];
+  const int n = (int)(hi - lo);
+  if (n <= 0) return;
+  const int r = threadIdx.x / C::L, sub = threadIdx.x % C::L;
+  const long rs = (long)H * dh;
+
+  // every thread walks all tiles, with or without a row of its own,
+  // so the __syncthreads() stay block-uniform; the segment's row
+  // chunks are dealt round-robin to the gridDim.z workgroups of this
+  // (graph, head), and a workgroup without a chunk leaves at once
+  for (int q0 = blockIdx.z * C::kRows; q0 < n;
+       q0 += gridDim.z * C::kRows) {
+    const int q = q0 + r;
+    const bool hasq = q < n;
+    const long qoff = ((lo + q) * (long)H + h) * dh;
+    float qv[C::DHL], acc[C::DHL];
+    load_row<C, T>(qv, Q + qoff, sub, dh, hasq, scale);
+#pragma unroll
+    for (int d = 0; d < C::DHL; ++d) acc[d] = 0.f;
+    float m = -1e30f, l = 0.f;
+    for (int t0 = 0; t0 < n; t0 += C::T) {
+      const int tn = n - t0 < C::T ? n - t0 : C::T;
+      const long toff = ((lo + t0) * (long)H + h) * dh;
+      __syncthreads();
+      stage_tile<C, T>(lK, K + toff, rs, tn, dh);
+      stage_tile<C, T>(lV, V + toff, rs, tn, dh);
+      __syncthreads();
+      if (hasq) {
+        for (int k = 0; k < tn; ++k) {
+          const int o = k * C::kRowStride + sub * C::kSub;
+          float s = dot_row<C>(qv, lK + o);
+          float m_new = s > m ? s : m;
+          float alpha = __expf(m - m_new);
+          float p = __expf(s - m_new);
+          l = l * alpha + p;
+#pragma unroll
+          for (int d = 0; d < C::DHL; ++d) acc[d] *= alpha;
+          axpy_row<C>(acc, p, lV + o);
+          m = m_new;
+        }
+      }
+    }
+    if (hasq) {
+      store_row<C, T>(O + qoff, acc, sub, dh, 1.f / l);
+      if (sub == 0) LSE[(lo + q) * (long)H + h] = m + logf(l);
+    }
+  }
+}
+
+// Backward pass 1, thread = query row, K/V tiled:
+//   D_i = sum_d dO_id O_id            (also written out for pass 2)
+//   dQ_i = scale * sum_j P_ij (dO_i.v_j - D_i) k_j
+template <typename C, typename T>
+__global__ __launch_bounds__(kBlock) void varlen_attn_dq_kernel(
+    const T* __restrict__ Q, const T* __restrict__ K,
+    const T* __restrict__ V, const T* __restrict__ O,
+    const float* __restrict__ LSE, const T* __restrict__ dO,
+    T* __restrict__ dQ, float* __restrict__ D,   // D [N, H]
+    const long* __restrict__ ptr, int H, int dh, float scale) {
+  __shared__ __align__(16) float lK[C::kTileFloats];
+  __shared__ __align__(16) float lV[C::kTileFloats];
+
+  const int h = blockIdx.y;
+  const long lo = ptr[blockIdx.x], hi = ptr[blockIdx.x + 1];
+  const int n = (int)(hi - lo);
+  if (n <= 0) return;
+  const int r = threadIdx.x / C::L, sub = threadIdx.x % C::L;
+  const long rs = (long)H * dh;
+
+  for (int q0 = blockIdx.z * C::kRows; q0 < n;
+       q0 += gridDim.z * C::kRows) {
+    const int q = q0 + r;
+    const bool hasq = q < n;
+    const long qoff = ((lo + q) * (long)H + h) * dh;
+    float qv[C::DHL], gv[C::DHL], dq[C::DHL];
+    load_row<C, T>(qv, Q + qoff, sub, dh, hasq, scale);
+    load_row<C, T>(gv, dO + qoff, sub, dh, hasq, 1.f);
+    float lse = 0.f, Di = 0.f;
+    if (hasq) {
+#pragma unroll
+      for (int d = 0; d < C::DHL; ++d) {
+        int c = sub * C::DHL + d;
+        if (c < dh) Di += gv[d] * to_f32<T>(O[qoff + c]);
+      }
+      if (C::L > 1) Di += __shfl_xor(Di, 1);
+      lse = LSE[(lo + q) * (long)H + h];
+      if (sub == 0) D[(lo + q) * (long)H + h] = Di;
+    }
+#pragma unroll
+    for (int d = 0; d < C::DHL; ++d) dq[d] = 0.f;
+    for (int t0 = 0; t0 < n; t0 += C::T) {
+      const int tn = n - t0 < C::T ? n - t0 : C::T;
+      const long toff = ((lo + t0) * (long)H + h) * dh;
+      __syncthreads();
+      stage_tile<C, T>(lK, K + toff, rs, tn, dh);
+      stage_tile<C, T>(lV, V + toff, rs, tn, dh);
+      __syncthreads();
+      if (hasq) {
+        for (int k = 0; k < tn; ++k) {
+          const int o = k * C::kRowStride + sub * C::kSub;
+          float s = dot_row<C>(qv, lK + o);
+          float dp = dot_row<C>(gv, lV + o);
+          float ds = __expf(s - lse) * (dp - Di);
+          axpy_row<C>(dq, ds, lK + o);
+        }
+      }
+    }
+    if (hasq) store_row<C, T>(dQ + qoff, dq, sub, dh, scale);
+  }
+}
+
+// Backward pass 2, thread = key row, Q/dO/LSE/D tiled:
+//   dV_j = sum_i P_ij dO_i
+//   dK_j = scale * sum_i P_ij (dO_i.v_j - D_i) q_i
+template <typename C, typename T>
+__global__ __launch_bounds__(kBlock) void varlen_attn_dkv_kernel(
+    const T* __restrict__ Q, const T* __restrict__ K,
+    const T* __restrict__ V, const float* __restrict__ LSE,
+    const float* __restrict__ D, const T* __restrict__ dO,
+    T* __restrict__ dK, T* __restrict__ dV,
+    const long* __restrict__ ptr, int H, int dh, float scale) {
+  __shared__ __align__(16) float lQ[C::kTileFloats];
+  __shared__ __align__(16) float lG[C::kTileFloats];
+  __shared__ float lLse[C::T];
+  __shared__ float lD[C::T];
+
+  const int h = blockIdx.y;
+  const long lo = ptr[blockIdx.x], hi = ptr[blockIdx.x + 1];
+  const int n = (int)(hi - lo);
+  if (n <= 0) return;
+  const int r = threadIdx.x / C::L, sub = threadIdx.x % C::L;
+  const long rs = (long)H * dh;
+
+  for (int j0 = blockIdx.z * C::kRows; j0 < n;
+       j0 += gridDim.z * C::kRows) {
+    const int j = j0 + r;
+    const bool hask = j < n;
+    const long koff = ((lo + j) * (long)H + h) * dh;
+    float kv[C::DHL], vv[C::DHL], dk[C::DHL], dv[C::DHL];
+    load_row<C, T>(kv, K + koff, sub, dh, hask, scale);
+    load_row<C, T>(vv, V + koff, sub, dh, hask, 1.f);
+#pragma unroll
+    for (int d = 0; d < C::DHL; ++d) dk[d] = dv[d] = 0.f;
+    for (int t0 = 0; t0 < n; t0 += C::T) {
+      const int tn = n - t0 < C::T ? n - t0 : C::T;
+      const long toff = ((lo + t0) * (long)H + h) * dh;
+      __syncthreads();
+      stage_tile<C, T>(lQ, Q + toff, rs, tn, dh);
+      stage_tile<C, T>(lG, dO + toff, rs, tn, dh);
+      for (int i = threadIdx.x; i < tn; i += kBlock) {
+        lLse[i] = LSE[(lo + t0 + i) * (long)H + h];
+        lD[i] = D[(lo + t0 + i) * (long)H + h];
+      }
+      __syncthreads();
+      if (hask) {
+        for (int i = 0; i < tn; ++i) {
+          const int o = i * C::kRowStride + sub * C::kSub;
+          float s = dot_row<C>(kv, lQ + o);
+          float dp = dot_row<C>(vv, lG + o);
+          float p = __expf(s - lLse[i]);
+          axpy_row<C>(dv, p, lG + o);
+          axpy_row<C>(dk, p * (dp - lD[i]), lQ + o);
+        }
+      }
+    }
+    if (hask) {
+      store_row<C, T>(dV + koff, dv, sub, dh, 1.f);
+      store_row<C, T>(dK + koff, dk, sub, dh, scale);
+    }
+  }
+}
+
+// A refused launch (e.g. LDS over the limit) must not hand back
+// uninitialised outputs.
+inline void check_launch(const char* what) {
+  hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, what, " launch failed: ",
+              hipGetErrorString(err));
+}
+
+// Calls f(VCfg instance) for the narrowest instance that holds dh.
+template <typename F>
+void with_instance(long dh, F&& f) {
+  TORCH_CHECK(dh >= 1 && dh <= VCfg128::kCap,
+              "varlen attention: head_dim must be in [1, 128]");
+  if (dh <= VCfg16::kCap) f(VCfg16{});
+  else if (dh <= VCfg32::kCap) f(VCfg32{});
+  else if (dh <= VCfg64::kCap) f(VCfg64{});
+  else f(VCfg128{});
+}
+
+void check_qkv(const torch::Tensor& Q, const torch::Tensor& K,
+               const torch::Tensor& V, const torch::Tensor& ptr) {
+  TORCH_CHECK(Q.is_cuda() && K.is_cuda() && V.is_cuda() && ptr.is_cuda());
+  TORCH_CHECK(Q.dim() == 3 && K.sizes() == Q.sizes() &&
+              V.sizes() == Q.sizes());
+  TORCH_CHECK(Q.is_contiguous() && K.is_contiguous() && V.is_contiguous());
+  TORCH_CHECK(Q.scalar_type() == at::ScalarType::Float ||
+              Q.scalar_type() == at::ScalarType::BFloat16,
+              "varlen attention expects fp32 or bf16 q/k/v");
+  TORCH_CHECK(K.scalar_type() == Q.scalar_type() &&
+              V.scalar_type() == Q.scalar_type());
+  TORCH_CHECK(ptr.scalar_type() == at::ScalarType::Long &&
+              ptr.dim() == 1 && ptr.numel() >= 1);
+}
+
+template <typename T>
+const T* cptr(const torch::Tensor& t) {
+  return reinterpret_cast<const T*>(t.data_ptr());
+}
+template <typename T>
+T* mptr(torch::Tensor& t) {
+  return reinterpret_cast<T*>(t.data_ptr());
+}
+
+// Workgroups per (graph, head).  Segment lengths live on the device,
+// so the split follows the mean length N / G, which the shapes give
+// without a sync: 1.5 mean-length's worth of row chunks, at most 8.
+// Each row is computed by one thread in one fixed order whatever the
+// split, so it does not change a single bit of the result.
+inline unsigned row_split(long N, long G, long rows) {
+  long z = (3 * N + 2 * G * rows - 1) / (2 * G * rows);
+  return (unsigned)std::min<long>(std::max<long>(z, 1), 8);
+}
+
+template <typename T>
+void launch_fwd(const torch::Tensor& Q, const torch::Tensor& K,
+                const torch::Tensor& V, torch::Tensor& O,
+                torch::Tensor& LSE, const torch::Tensor& ptr) {
+  const int H = Q.size(1), dh = Q.size(2);
+  const long G = ptr.numel() - 1;
+  const float scale = 1.0f / std::sqrt((float)dh);
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  with_instance(dh, [&](auto c) {
+    using C = decltype(c);
+    const dim3 grid(G, H, row_split(Q.size(0), G, C::kRows));
+    hipLaunchKernelGGL((varlen_attn_fwd_kernel<C, T>), grid,
+                       dim3(kBlock), 0, stream, cptr<T>(Q), cptr<T>(K),
+                       cptr<T>(V), mptr<T>(O), LSE.data_ptr<float>(),
+                       ptr.data_ptr<long>(), H, dh, scale);
+  });
+  check_launch("varlen_attention_fwd");
+}
+
+template <typename T>
+void launch_bwd(const torch::Tensor& Q, const torch::Tensor& K,
+                const torch::Tensor& V, const torch::Tensor& O,
+                const torch::Tensor& LSE, const torch::Tensor& dO,
+                torch::Tensor& dQ, torch::Tensor& dK, torch::Tensor& dV,
+                torch::Tensor& D, const torch::Tensor& ptr) {
+  const int H = Q.size(1), dh = Q.size(2);
+  const long G = ptr.numel() - 1;
+  const float scale = 1.0f / std::sqrt((float)dh);
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  with_instance(dh, [&](auto c) {
+    using C = decltype(c);
+    const dim3 grid(G, H, row_split(Q.size(0), G, C::kRows));
+    hipLaunchKernelGGL((varlen_attn_dq_kernel<C, T>), grid,
+                       dim3(kBlock), 0, stream, cptr<T>(Q), cptr<T>(K),
+                       cptr<T>(V), cptr<T>(O), LSE.data_ptr<float>(),
+                       cptr<T>(dO), mptr<T>(dQ), D.data_ptr<float>(),
+                       ptr.data_ptr<long>(), H, dh, scale);
+    check_launch("varlen_attention_bwd (dQ pass)");
+    // same stream: D is complete before this pass reads it
+    hipLaunchKernelGGL((varlen_attn_dkv_kernel<C, T>), grid,
+                       dim3(kBlock), 0, stream, cptr<T>(Q), cptr<T>(K),
+                       cptr<T>(V), LSE.data_ptr<float>(),
+                       D.data_ptr<float>(), cptr<T>(dO), mptr<T>(dK),
+                       mptr<T>(dV), ptr.data_ptr<long>(), H, dh, scale);
+    check_launch("varlen_attention_bwd (dK/dV pass)");
+  });
+}
+
 }  // namespace
+
+// LDS bytes (static; these kernels use no dynamic LDS) of the instance
+// that serves head_dim dh.  pass: 0 forward, 1 dQ, 2 dK/dV.
+long varlen_attention_lds_bytes(long dh, long pass) {
+  TORCH_CHECK(pass >= 0 && pass <= 2, "pass must be 0, 1 or 2");
+  long bytes = 0;
+  with_instance(dh, [&](auto c) {
+    using C = decltype(c);
+    bytes = pass == 0 ? C::kLdsFwd : pass == 1 ? C::kLdsDq : C::kLdsDkv;
+  });
+  return bytes;
+}
+
+// {tile rows T, rows per workgroup pass B} of the instance serving dh.
+std::vector<long> varlen_attention_tiling(long dh) {
+  std::vector<long> out;
+  with_instance(dh, [&](auto c) {
+    using C = decltype(c);
+    out = {C::T, C::kRows};
+  });
+  return out;
+}
+
+std::vector<torch::Tensor> varlen_attention_fwd(
+    torch::Tensor Q, torch::Tensor K, torch::Tensor V,
+    torch::Tensor ptr) {
+  check_qkv(Q, K, V, ptr);
+  const long N = Q.size(0), H = Q.size(1), dh = Q.size(2);
+  TORCH_CHECK(H >= 1 && H <= 65535, "head count must be in [1, 65535]");
+  TORCH_CHECK(varlen_attention_lds_bytes(dh, 0) <= kLdsBudget,
+              "varlen_attention_fwd: LDS over 160 KiB");
+  auto O = torch::empty_like(Q);
+  auto LSE = torch::empty({N, H}, Q.options().dtype(torch::kFloat));
+  if (N == 0 || ptr.numel() == 1) return {O, LSE};
+  auto p = ptr.contiguous();
+  if (Q.scalar_type() == at::ScalarType::Float)
+    launch_fwd<float>(Q, K, V, O, LSE, p);
+  else
+    launch_fwd<__hip_bfloat16>(Q, K, V, O, LSE, p);
+  return {O, LSE};
+}
+
+std::vector<torch::Tensor> varlen_attention_bwd(
+    torch::Tensor Q, torch::Tensor K, torch::Tensor V, torch::Tensor O,
+    torch::Tensor LSE, torch::Tensor dO, torch::Tensor ptr) {
+  check_qkv(Q, K, V, ptr);
+  const long N = Q.size(0), H = Q.size(1), dh = Q.size(2);
+  TORCH_CHECK(H >= 1 && H <= 65535, "head count must be in [1, 65535]");
+  for (const torch::Tensor* t : {&O, &dO})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->sizes() == Q.sizes() &&
+                t->scalar_type() == Q.scalar_type(),
+                "varlen_attention_bwd: O and dO must match q");
+  TORCH_CHECK(LSE.is_cuda() && LSE.is_contiguous() &&
+              LSE.scalar_type() == at::ScalarType::Float &&
+              LSE.dim() == 2 && LSE.size(0) == N && LSE.size(1) == H,
+              "varlen_attention_bwd: LSE must be [N, H] fp32");
+  TORCH_CHECK(varlen_attention_lds_bytes(dh, 1) <= kLdsBudget &&
+              varlen_attention_lds_bytes(dh, 2) <= kLdsBudget,
+              "varlen_attention_bwd: LDS over 160 KiB");
+  auto dQ = torch::empty_like(Q);
+  auto dK = torch::empty_like(Q);
+  auto dV = torch::empty_like(Q);
+  if (N == 0 || ptr.numel() == 1) return {dQ, dK, dV};
+  auto D = torch::empty_like(LSE);
+  auto p = ptr.contiguous();
+  if (Q.scalar_type() == at::ScalarType::Float)
+    launch_bwd<float>(Q, K, V, O, LSE, dO, dQ, dK, dV, D, p);
+  else
+    launch_bwd<__hip_bfloat16>(Q, K, V, O, LSE, dO, dQ, dK, dV, D, p);
+  return {dQ, dK, dV};
+}
 
 torch::Tensor varlen_attention(torch::Tensor Q, torch::Tensor K,
                                torch::Tensor V, torch::Tensor ptr) {

@@ -2,20 +2,33 @@
 
 Dense-batch attention (reference hydragnn/globalAtt/gps.py:140) pads
 every graph to the largest one in the batch; for molecular batches that
-wastes both HBM traffic and FLOPs.  The HIP kernel
-(csrc/varlen_attn.hip) runs one (graph, head) per workgroup with K/V
-staged in LDS and an online softmax over exactly the graph's nodes.
+wastes both HBM traffic and FLOPs.  The HIP kernels
+(csrc/varlen_attn.hip) run one (graph, head) per workgroup with the
+other side staged in LDS tiles, over exactly the graph's nodes, for
+fp32 or bf16, head_dim <= 128 and any segment length.
 
-Backward recomputes through a pure-torch reference (dense-batch
-explicit-softmax attention with a finite mask bias — double
-differentiable on every backend), so first and second order gradients
-are exact without a hand-written backward kernel; the recompute only
-triggers on the GPS training path, which is not the headline bench.
+Orders of differentiation:
+
+* forward: ``varlen_attention_fwd`` -> (O, LSE), LSE the row
+  log-sum-exp of the scaled logits;
+* first order: ``varlen_attention_bwd``, two atomic-free passes that
+  recompute P from LSE (``_VarlenAttnBwd.forward``) -- no host sync, no
+  dense re-padding;
+* second order (force-style training): ``_VarlenAttnBwd.backward``
+  recomputes the attention through a pure-torch reference (dense-batch
+  explicit softmax with a finite mask bias, query-chunked above 1024
+  nodes per segment) and differentiates that twice.
+
+``HYDRAGNN_VARLEN_ATTN_BWD=0`` restores the first-order recompute
+backward (the torch reference differentiated once).  On CPU tensors the
+same two autograd Functions run on pure-torch doubles of the two entry
+points, which is what the autograd-closure tests check without a GPU.
 """
 
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 
@@ -23,7 +36,7 @@ from ._extension import get_extension
 from ..data import to_dense_batch
 
 MAX_SEG = None  # r2: K/V tiling removed the segment cap
-MAX_DH = 64
+MAX_DH = 128
 
 
 def torch_varlen_attention_chunked(q, k, v, batch, chunk=512):
@@ -73,55 +86,172 @@ def torch_varlen_attention(q: torch.Tensor, k: torch.Tensor,
     return out[mask]
 
 
+def _segments(ptr):
+    p = ptr.tolist()
+    return [(lo, hi) for lo, hi in zip(p[:-1], p[1:]) if hi > lo]
+
+
+def torch_varlen_attention_fwd(q, k, v, ptr):
+    """Pure-torch double of the ``varlen_attention_fwd`` entry point:
+    (O [N, H, dh], LSE [N, H]) per segment of the rowptr ``ptr``; LSE
+    in q's dtype (the kernel's is fp32)."""
+    N, H, dh = q.shape
+    scale = 1.0 / math.sqrt(dh)
+    out = torch.empty_like(q)
+    lse = q.new_empty(N, H)
+    for lo, hi in _segments(ptr):
+        qg, kg, vg = (t[lo:hi].transpose(0, 1) for t in (q, k, v))
+        s = qg @ kg.transpose(-1, -2) * scale        # [H, n, n]
+        ls = torch.logsumexp(s, dim=-1)              # [H, n]
+        out[lo:hi] = (torch.exp(s - ls[..., None]) @ vg).transpose(0, 1)
+        lse[lo:hi] = ls.transpose(0, 1)
+    return out, lse
+
+
+def torch_varlen_attention_bwd(q, k, v, out, lse, dout, ptr):
+    """Pure-torch double of the ``varlen_attention_bwd`` entry point:
+    with s = scale q k^T, P = exp(s - LSE), D = rowsum(dO * O),
+    dV = P^T dO, dS = P (dO V^T - D), dQ = scale dS K,
+    dK = scale dS^T Q, per segment."""
+    N, H, dh = q.shape
+    scale = 1.0 / math.sqrt(dh)
+    dq, dk, dv = (torch.empty_like(t) for t in (q, k, v))
+    for lo, hi in _segments(ptr):
+        qg, kg, vg, og, gg = (t[lo:hi].transpose(0, 1)
+                              for t in (q, k, v, out, dout))
+        p = torch.exp(qg @ kg.transpose(-1, -2) * scale
+                      - lse[lo:hi].transpose(0, 1)[..., None])
+        d = (gg * og).sum(-1, keepdim=True)          # [H, n, 1]
+        ds = p * (gg @ vg.transpose(-1, -2) - d)
+        dv[lo:hi] = (p.transpose(-1, -2) @ gg).transpose(0, 1)
+        dq[lo:hi] = (ds @ kg).transpose(0, 1) * scale
+        dk[lo:hi] = (ds.transpose(-1, -2) @ qg).transpose(0, 1) * scale
+    return dq, dk, dv
+
+
+def varlen_tiling(head_dim: int):
+    """(tile rows T, rows per workgroup pass B) of the kernel instance
+    that serves ``head_dim``."""
+    t, b = get_extension(required=True).varlen_attention_tiling(head_dim)
+    return t, b
+
+
+def _kernel_backward_enabled() -> bool:
+    return os.environ.get("HYDRAGNN_VARLEN_ATTN_BWD", "1") != "0"
+
+
+def _recompute_out(q, k, v, batch):
+    """The double-differentiable torch recompute of the attention
+    (syncs on the segment sizes to pick the bounded-memory path)."""
+    max_seg = int(torch.bincount(batch).max()) if batch.numel() else 0
+    if max_seg > 1024:
+        # dense recompute would materialize maxN^2 logits per
+        # graph; chunked exact path keeps memory bounded
+        return torch_varlen_attention_chunked(q, k, v, batch)
+    return torch_varlen_attention(q, k, v, batch)
+
+
 class _VarlenAttn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, ptr, batch):
-        ext = get_extension(required=True)
-        out = ext.varlen_attention(q.contiguous(), k.contiguous(),
-                                   v.contiguous(), ptr)
-        ctx.save_for_backward(q, k, v, batch)
+        if q.is_cuda:
+            ext = get_extension(required=True)
+            out, lse = ext.varlen_attention_fwd(
+                q.contiguous(), k.contiguous(), v.contiguous(), ptr)
+        else:
+            out, lse = torch_varlen_attention_fwd(q, k, v, ptr)
+        ctx.save_for_backward(q, k, v, out, lse, ptr, batch)
         return out
 
     @staticmethod
     def backward(ctx, g):
+        q, k, v, out, lse, ptr, batch = ctx.saved_tensors
+        if _kernel_backward_enabled():
+            dq, dk, dv = _VarlenAttnBwd.apply(
+                q, k, v, out, lse, g.contiguous(), ptr, batch)
+            return dq, dk, dv, None, None
         # recompute through the torch reference, differentiating w.r.t.
         # the SAVED tensors (not detached copies) so the second-order
         # graph stays connected for force-style double backward
-        q, k, v, batch = ctx.saved_tensors
         need = ctx.needs_input_grad[:3]
-        max_seg = int(torch.bincount(batch).max()) \
-            if batch.numel() else 0
         with torch.enable_grad():
-            if max_seg > 1024:
-                # dense recompute would materialize maxN^2 logits per
-                # graph; chunked exact path keeps memory bounded
-                out = torch_varlen_attention_chunked(q, k, v, batch)
-            else:
-                out = torch_varlen_attention(q, k, v, batch)
+            ref = _recompute_out(q, k, v, batch)
             inputs = [t for t, n in zip((q, k, v), need) if n]
             grads = iter(torch.autograd.grad(
-                out, inputs, g, create_graph=torch.is_grad_enabled(),
+                ref, inputs, g, create_graph=torch.is_grad_enabled(),
                 allow_unused=True))
         res = [next(grads) if n else None for n in need]
         return res[0], res[1], res[2], None, None
 
 
-def varlen_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                     ptr: torch.Tensor, batch: torch.Tensor):
-    """[N, H, dh] q/k/v, graph rowptr [G+1] and per-node graph index
-    [N] -> [N, H, dh].  HIP kernel on GPU (fp32), torch reference on
-    CPU."""
-    if not q.is_cuda:
-        return torch_varlen_attention(q, k, v, batch)
-    if q.dtype not in (torch.float32, torch.bfloat16):
+class _VarlenAttnBwd(torch.autograd.Function):
+    """(q, k, v, out, lse, g) -> (dq, dk, dv) on the backward kernels;
+    its own backward (the double backward) is torch ops."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, out, lse, g, ptr, batch):
+        if q.is_cuda:
+            ext = get_extension(required=True)
+            dq, dk, dv = ext.varlen_attention_bwd(
+                q.contiguous(), k.contiguous(), v.contiguous(),
+                out, lse, g, ptr)
+        else:
+            dq, dk, dv = torch_varlen_attention_bwd(
+                q, k, v, out, lse, g, ptr)
+        ctx.save_for_backward(q, k, v, g, batch)
+        ctx.set_materialize_grads(False)
+        return dq, dk, dv
+
+    @staticmethod
+    def backward(ctx, *cots):
+        # out and lse are functions of (q, k, v): the recompute below
+        # carries that dependence, so they get no gradient of their own.
+        # The cotangent g enters as a fresh leaf -- its own history
+        # (e.g. g = 2 * out) is differentiated by the caller's graph
+        # from the gradient returned for it here, not a second time
+        # inside this recompute.
+        *qkv, g, batch = ctx.saved_tensors
+        pairs = [(i, c) for i, c in enumerate(cots) if c is not None]
+        if not pairs:
+            return (None,) * 8
+        with torch.enable_grad():
+            g = g.detach().requires_grad_(True)
+            # an operand outside the caller's graph still has to be
+            # differentiated once to form the first-order gradients
+            qkv = [t if t.requires_grad else
+                   t.detach().requires_grad_(True) for t in qkv]
+            ref = _recompute_out(*qkv, batch)
+            first = torch.autograd.grad(
+                ref, [qkv[i] for i, _ in pairs], g, create_graph=True)
+            gq, gk, gv, gg = torch.autograd.grad(
+                first, (*qkv, g), [c for _, c in pairs],
+                create_graph=torch.is_grad_enabled(), allow_unused=True)
+        return gq, gk, gv, None, None, gg, None, None
+
+
+def varlen_attention_fn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                        ptr: torch.Tensor, batch: torch.Tensor):
+    """Attention through the autograd Function pair on any device:
+    HIP kernels for GPU tensors (fp32/bf16 native, other dtypes via
+    fp32), their pure-torch doubles for CPU tensors."""
+    if q.is_cuda and q.dtype not in (torch.float32, torch.bfloat16):
         orig_dtype = q.dtype
         q, k, v = (t.float() for t in (q, k, v))
         return _VarlenAttn.apply(q, k, v, ptr, batch).to(orig_dtype)
     return _VarlenAttn.apply(q, k, v, ptr, batch)
 
 
+def varlen_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                     ptr: torch.Tensor, batch: torch.Tensor):
+    """[N, H, dh] q/k/v, graph rowptr [G+1] and per-node graph index
+    [N] -> [N, H, dh].  HIP kernels on GPU (fp32 or bf16, head_dim <=
+    128, forward and first-order backward), torch reference on CPU."""
+    if not q.is_cuda:
+        return torch_varlen_attention(q, k, v, batch)
+    return varlen_attention_fn(q, k, v, ptr, batch)
+
+
 def varlen_eligible(head_dim: int, max_seg: int, device) -> bool:
-    import os
     if os.environ.get("HYDRAGNN_VARLEN_ATTN", "1") == "0":
         return False
     if not (isinstance(device, torch.device) and device.type == "cuda"):

@@ -5,15 +5,19 @@
 //  - wave = 64 lanes; block sizes are multiples of 64.
 //  - memory-bound ops: grid-stride loops, coalesced along the feature
 //    dim, vectorized where dtype/shape allow.
-//  - bf16/f16 scatter accumulates in fp32 (atomicAdd on packed halves is
-//    both slow and lossy), cast once at the end.
+//  - bf16/f16 sums accumulate in fp32 on every route (atomicAdd on
+//    packed halves is both slow and lossy), cast once at the end; a
+//    mean is divided in the accumulator type before that one cast.
+//  - a launch of zero elements is skipped; every launch is checked.
 //  - grid capped at ~2048 blocks with grid-stride (guide G11).
 //
 // Reference behavior being reimplemented (not copied):
 //   torch_scatter.scatter / index_add_ call sites listed in SURVEY.md §2c.
 
 #include <torch/extension.h>
+#include <ATen/OpMathType.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPException.h>
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
@@ -27,6 +31,18 @@ constexpr int kBlock = 256;
 inline int n_blocks(long total, int block, int cap = 2048) {
   long b = (total + block - 1) / block;
   return (int)std::min<long>(b, cap);
+}
+
+// elements of one row: the product of the trailing dims (defined for a
+// tensor of zero rows too)
+inline long row_elems(const torch::Tensor& t) {
+  long f = 1;
+  for (int64_t d = 1; d < t.dim(); ++d) f *= t.size(d);
+  return f;
+}
+
+inline bool aligned16(const void* p) {
+  return reinterpret_cast<uintptr_t>(p) % 16 == 0;
 }
 
 // -------------------------------------------------------------------------
@@ -45,7 +61,8 @@ __global__ void gather_kernel(const T* __restrict__ src,
   }
 }
 
-// float4-vectorized variant for F % 4 == 0 (16B/lane coalescing).
+// float4-vectorized variant for rows that are a multiple of 16 bytes
+// on 16-byte-aligned bases (16B/lane coalescing).
 template <typename V>
 __global__ void gather_kernel_vec(const V* __restrict__ src,
                                   const long* __restrict__ index,
@@ -105,8 +122,9 @@ __global__ void scatter_add_f16_kernel(const __half* __restrict__ src,
 // CSR segment sum over dst-sorted edges: deterministic and
 // contention-free (vs the atomic path).  Thread per (row, feature);
 // consecutive edges of a row are contiguous src rows -> coalesced
-// within each step of the edge loop.
-template <typename T, typename ACC>
+// within each step of the edge loop.  ACC is fp32 for bf16/f16.  MEAN
+// divides the accumulator by the row length before the one store.
+template <typename T, typename ACC, bool MEAN>
 __global__ void segment_sum_csr_kernel(const T* __restrict__ src,
                                        const long* __restrict__ rowptr,
                                        T* __restrict__ out, long N,
@@ -119,25 +137,8 @@ __global__ void segment_sum_csr_kernel(const T* __restrict__ src,
     ACC acc = (ACC)0;
     long lo = rowptr[n], hi = rowptr[n + 1];
     for (long e = lo; e < hi; ++e) acc += (ACC)src[e * F + f];
+    if (MEAN && hi > lo) acc = acc / (ACC)(hi - lo);
     out[i] = (T)acc;
-  }
-}
-
-template <>
-__global__ void segment_sum_csr_kernel<__hip_bfloat16, float>(
-    const __hip_bfloat16* __restrict__ src,
-    const long* __restrict__ rowptr, __hip_bfloat16* __restrict__ out,
-    long N, long F) {
-  long total = N * F;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long)gridDim.x * blockDim.x) {
-    long n = i / F;
-    long f = i - n * F;
-    float acc = 0.f;
-    long lo = rowptr[n], hi = rowptr[n + 1];
-    for (long e = lo; e < hi; ++e)
-      acc += __bfloat162float(src[e * F + f]);
-    out[i] = __float2bfloat16(acc);
   }
 }
 
@@ -162,24 +163,6 @@ __global__ void segment_sum_csr_idx_kernel(
   }
 }
 
-template <>
-__global__ void segment_sum_csr_idx_kernel<__hip_bfloat16, float>(
-    const __hip_bfloat16* __restrict__ src,
-    const long* __restrict__ rowptr, const long* __restrict__ perm,
-    __hip_bfloat16* __restrict__ out, long N, long F) {
-  long total = N * F;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long)gridDim.x * blockDim.x) {
-    long n = i / F;
-    long f = i - n * F;
-    float acc = 0.f;
-    long lo = rowptr[n], hi = rowptr[n + 1];
-    for (long e = lo; e < hi; ++e)
-      acc += __bfloat162float(src[perm[e] * F + f]);
-    out[i] = __float2bfloat16(acc);
-  }
-}
-
 __global__ void count_kernel(const long* __restrict__ index,
                              float* __restrict__ count, long E) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < E;
@@ -188,6 +171,7 @@ __global__ void count_kernel(const long* __restrict__ index,
   }
 }
 
+// in place on the accumulator (fp32 or fp64), before any cast
 template <typename T>
 __global__ void divide_rows_kernel(T* __restrict__ out,
                                    const float* __restrict__ count, long N,
@@ -205,7 +189,12 @@ __global__ void divide_rows_kernel(T* __restrict__ out,
 // scatter min/max with argext — two-pass:
 //   pass 1: atomic extreme on float-ordered bits
 //   pass 2: first (lowest e) matching edge wins the arg slot (atomicMin)
+//   finalize: a slot no edge claimed (arg still kNoArg) is an empty
+//   segment -> 0 / -1; the value cannot tell, a segment of all -inf
+//   under max leaves the bits at their fill
 // -------------------------------------------------------------------------
+constexpr unsigned long long kNoArg = 0x7fffffffffffffffull;
+
 __device__ inline unsigned int float_flip(float f) {
   unsigned int u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // order-preserving
@@ -297,12 +286,10 @@ __global__ void scatter_max_pass2_f64(const double* __restrict__ src,
 __global__ void scatter_max_finalize_f64(
     const unsigned long long* __restrict__ bits,
     const unsigned long long* __restrict__ arg, double* __restrict__ out,
-    long* __restrict__ arg_out, long total, bool is_max) {
-  unsigned long long empty =
-      is_max ? double_flip(-INFINITY) : double_flip(INFINITY);
+    long* __restrict__ arg_out, long total) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long)gridDim.x * blockDim.x) {
-    bool present = bits[i] != empty;
+    bool present = arg[i] != kNoArg;
     out[i] = present ? double_unflip(bits[i]) : 0.0;
     arg_out[i] = present ? (long)arg[i] : -1;
   }
@@ -311,13 +298,10 @@ __global__ void scatter_max_finalize_f64(
 __global__ void scatter_max_finalize(const unsigned int* __restrict__ bits,
                                      const unsigned long long* __restrict__ arg,
                                      float* __restrict__ out,
-                                     long* __restrict__ arg_out, long total,
-                                     bool is_max) {
-  unsigned int empty =
-      is_max ? float_flip(-INFINITY) : float_flip(INFINITY);
+                                     long* __restrict__ arg_out, long total) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long)gridDim.x * blockDim.x) {
-    bool present = bits[i] != empty;
+    bool present = arg[i] != kNoArg;
     out[i] = present ? float_unflip(bits[i]) : 0.0f;
     arg_out[i] = present ? (long)arg[i] : -1;
   }
@@ -387,157 +371,154 @@ static hipStream_t cur_stream() {
   return at::hip::getCurrentHIPStream().stream();
 }
 
+#define LAUNCH(kernel, total, cap, ...)                                   \
+  do {                                                                    \
+    hipLaunchKernelGGL(kernel, dim3(n_blocks((total), kBlock, (cap))),    \
+                       dim3(kBlock), 0, cur_stream(), __VA_ARGS__);       \
+    C10_HIP_KERNEL_LAUNCH_CHECK();                                        \
+  } while (0)
+
 torch::Tensor gather_fwd(torch::Tensor src, torch::Tensor index) {
   CHECK_CUDA(src); CHECK_CONTIG(src); CHECK_CUDA(index);
   TORCH_CHECK(index.dtype() == torch::kLong);
+  TORCH_CHECK(src.dim() >= 1, "src needs a row dim");
   long E = index.numel();
-  long F = src.numel() / std::max<long>(src.size(0), 1);
+  long F = row_elems(src);
   auto sizes = src.sizes().vec();
   sizes[0] = E;
   auto out = torch::empty(sizes, src.options());
-  if (E == 0) return out;
+  if (E * F == 0) return out;
   auto idx = index.contiguous();
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::BFloat16, at::ScalarType::Half, src.scalar_type(),
       "gather_fwd", [&] {
         long bytes = F * sizeof(scalar_t);
-        if (bytes % 16 == 0) {
+        const scalar_t* sp = src.data_ptr<scalar_t>();
+        scalar_t* op = out.data_ptr<scalar_t>();
+        // a contiguous view into a flat buffer need not start on 16 B
+        if (bytes % 16 == 0 && aligned16(sp) && aligned16(op)) {
           long Fv = bytes / 16;
-          hipLaunchKernelGGL(gather_kernel_vec<float4>,
-                             dim3(n_blocks(E * Fv, kBlock)), dim3(kBlock), 0,
-                             cur_stream(),
-                             reinterpret_cast<const float4*>(src.data_ptr<scalar_t>()),
-                             idx.data_ptr<long>(),
-                             reinterpret_cast<float4*>(out.data_ptr<scalar_t>()),
-                             E, Fv);
+          LAUNCH(gather_kernel_vec<float4>, E * Fv, 2048,
+                 reinterpret_cast<const float4*>(sp), idx.data_ptr<long>(),
+                 reinterpret_cast<float4*>(op), E, Fv);
         } else {
-          hipLaunchKernelGGL(gather_kernel<scalar_t>,
-                             dim3(n_blocks(E * F, kBlock)), dim3(kBlock), 0,
-                             cur_stream(), src.data_ptr<scalar_t>(),
-                             idx.data_ptr<long>(), out.data_ptr<scalar_t>(), E,
-                             F);
+          LAUNCH(gather_kernel<scalar_t>, E * F, 2048, sp,
+                 idx.data_ptr<long>(), op, E, F);
         }
       });
   return out;
 }
 
-torch::Tensor scatter_sum_fwd(torch::Tensor src, torch::Tensor index,
-                              long dim_size) {
+// Atomic segment sum into a zeroed accumulator: fp32 for bf16/f16
+// sources, the source dtype otherwise.
+static torch::Tensor scatter_sum_acc(const torch::Tensor& src,
+                                     const torch::Tensor& index,
+                                     long dim_size) {
   CHECK_CUDA(src); CHECK_CONTIG(src); CHECK_CUDA(index);
+  TORCH_CHECK(index.dtype() == torch::kLong);
+  TORCH_CHECK(src.dim() >= 1 && index.numel() == src.size(0),
+              "index must hold one entry per src row");
   long E = index.numel();
-  long F = E > 0 ? src.numel() / src.size(0) : 1;
+  long F = row_elems(src);
   auto sizes = src.sizes().vec();
   sizes[0] = dim_size;
+  auto st = src.scalar_type();
+  bool half = st == at::ScalarType::BFloat16 || st == at::ScalarType::Half;
+  auto acc = torch::zeros(
+      sizes, half ? src.options().dtype(torch::kFloat) : src.options());
+  if (E * F == 0 || dim_size == 0) return acc;
   auto idx = index.contiguous();
-  if (src.scalar_type() == at::ScalarType::BFloat16 ||
-      src.scalar_type() == at::ScalarType::Half) {
-    auto acc = torch::zeros(sizes, src.options().dtype(torch::kFloat));
-    if (E > 0) {
-      if (src.scalar_type() == at::ScalarType::BFloat16) {
-        hipLaunchKernelGGL(scatter_add_bf16_kernel,
-                           dim3(n_blocks(E * F, kBlock)), dim3(kBlock), 0,
-                           cur_stream(),
-                           reinterpret_cast<const __hip_bfloat16*>(src.data_ptr()),
-                           idx.data_ptr<long>(), acc.data_ptr<float>(), E, F);
-      } else {
-        hipLaunchKernelGGL(scatter_add_f16_kernel,
-                           dim3(n_blocks(E * F, kBlock)), dim3(kBlock), 0,
-                           cur_stream(),
-                           reinterpret_cast<const __half*>(src.data_ptr()),
-                           idx.data_ptr<long>(), acc.data_ptr<float>(), E, F);
-      }
-    }
-    return acc.to(src.scalar_type());
+  if (st == at::ScalarType::BFloat16) {
+    LAUNCH(scatter_add_bf16_kernel, E * F, 2048,
+           reinterpret_cast<const __hip_bfloat16*>(src.data_ptr()),
+           idx.data_ptr<long>(), acc.data_ptr<float>(), E, F);
+  } else if (st == at::ScalarType::Half) {
+    LAUNCH(scatter_add_f16_kernel, E * F, 2048,
+           reinterpret_cast<const __half*>(src.data_ptr()),
+           idx.data_ptr<long>(), acc.data_ptr<float>(), E, F);
+  } else {
+    AT_DISPATCH_FLOATING_TYPES(st, "scatter_sum_fwd", [&] {
+      LAUNCH(scatter_add_kernel<scalar_t>, E * F, 2048,
+             src.data_ptr<scalar_t>(), idx.data_ptr<long>(),
+             acc.data_ptr<scalar_t>(), E, F);
+    });
   }
-  auto out = torch::zeros(sizes, src.options());
-  if (E == 0) return out;
-  AT_DISPATCH_FLOATING_TYPES(src.scalar_type(), "scatter_sum_fwd", [&] {
-    hipLaunchKernelGGL(scatter_add_kernel<scalar_t>,
-                       dim3(n_blocks(E * F, kBlock)), dim3(kBlock), 0,
-                       cur_stream(), src.data_ptr<scalar_t>(),
-                       idx.data_ptr<long>(), out.data_ptr<scalar_t>(), E, F);
-  });
-  return out;
+  return acc;
 }
 
+torch::Tensor scatter_sum_fwd(torch::Tensor src, torch::Tensor index,
+                              long dim_size) {
+  return scatter_sum_acc(src, index, dim_size).to(src.scalar_type());
+}
+
+// mean = true (sorted route only): each row's sum is divided by its
+// length in the accumulator type before the store.
 torch::Tensor segment_sum_csr(torch::Tensor src, torch::Tensor rowptr,
-                              c10::optional<torch::Tensor> perm) {
-  CHECK_CUDA(src); CHECK_CONTIG(src);
+                              c10::optional<torch::Tensor> perm,
+                              bool mean) {
+  CHECK_CUDA(src); CHECK_CONTIG(src); CHECK_CUDA(rowptr);
+  TORCH_CHECK(rowptr.dtype() == torch::kLong && rowptr.numel() >= 1,
+              "rowptr must be int64 [N + 1]");
+  TORCH_CHECK(src.dim() >= 1, "src needs a row dim");
+  TORCH_CHECK(!(mean && perm.has_value()),
+              "the mean variant takes sorted rows, not a perm");
   long N = rowptr.numel() - 1;
-  long F = src.numel() / std::max<long>(src.size(0), 1);
+  long F = row_elems(src);
   auto sizes = src.sizes().vec();
   sizes[0] = N;
+  // nothing to sum: every row is empty
+  if (N * F == 0 || src.size(0) == 0) return torch::zeros(sizes, src.options());
   auto out = torch::empty(sizes, src.options());
   auto rp = rowptr.contiguous();
-  if (N == 0) return out;
   torch::Tensor pc;
   const long* perm_ptr = nullptr;
   if (perm.has_value()) {
+    CHECK_CUDA((*perm));
+    TORCH_CHECK(perm->dtype() == torch::kLong);
     pc = perm->contiguous();
     perm_ptr = pc.data_ptr<long>();
   }
-  if (src.scalar_type() == at::ScalarType::BFloat16) {
-    if (perm_ptr) {
-      hipLaunchKernelGGL(
-          (segment_sum_csr_idx_kernel<__hip_bfloat16, float>),
-          dim3(n_blocks(N * F, kBlock, 8192)), dim3(kBlock), 0,
-          cur_stream(),
-          reinterpret_cast<const __hip_bfloat16*>(src.data_ptr()),
-          rp.data_ptr<long>(), perm_ptr,
-          reinterpret_cast<__hip_bfloat16*>(out.data_ptr()), N, F);
-    } else {
-      hipLaunchKernelGGL(
-          (segment_sum_csr_kernel<__hip_bfloat16, float>),
-          dim3(n_blocks(N * F, kBlock, 8192)), dim3(kBlock), 0,
-          cur_stream(),
-          reinterpret_cast<const __hip_bfloat16*>(src.data_ptr()),
-          rp.data_ptr<long>(),
-          reinterpret_cast<__hip_bfloat16*>(out.data_ptr()), N, F);
-    }
-    return out;
-  }
-  AT_DISPATCH_FLOATING_TYPES_AND(at::ScalarType::Half, src.scalar_type(),
-                                 "segment_sum_csr", [&] {
-    if (perm_ptr) {
-      hipLaunchKernelGGL((segment_sum_csr_idx_kernel<scalar_t, scalar_t>),
-                         dim3(n_blocks(N * F, kBlock, 8192)), dim3(kBlock),
-                         0, cur_stream(), src.data_ptr<scalar_t>(),
-                         rp.data_ptr<long>(), perm_ptr,
-                         out.data_ptr<scalar_t>(), N, F);
-    } else {
-      hipLaunchKernelGGL((segment_sum_csr_kernel<scalar_t, scalar_t>),
-                         dim3(n_blocks(N * F, kBlock, 8192)), dim3(kBlock),
-                         0, cur_stream(), src.data_ptr<scalar_t>(),
-                         rp.data_ptr<long>(), out.data_ptr<scalar_t>(), N,
-                         F);
-    }
-  });
+  AT_DISPATCH_FLOATING_TYPES_AND2(
+      at::ScalarType::BFloat16, at::ScalarType::Half, src.scalar_type(),
+      "segment_sum_csr", [&] {
+        using acc_t = at::opmath_type<scalar_t>;  // fp32 for bf16/f16
+        const scalar_t* sp = src.data_ptr<scalar_t>();
+        scalar_t* op = out.data_ptr<scalar_t>();
+        if (perm_ptr) {
+          LAUNCH((segment_sum_csr_idx_kernel<scalar_t, acc_t>), N * F, 8192,
+                 sp, rp.data_ptr<long>(), perm_ptr, op, N, F);
+        } else if (mean) {
+          LAUNCH((segment_sum_csr_kernel<scalar_t, acc_t, true>), N * F,
+                 8192, sp, rp.data_ptr<long>(), op, N, F);
+        } else {
+          LAUNCH((segment_sum_csr_kernel<scalar_t, acc_t, false>), N * F,
+                 8192, sp, rp.data_ptr<long>(), op, N, F);
+        }
+      });
   return out;
 }
 
 std::vector<torch::Tensor> scatter_mean_fwd(torch::Tensor src,
                                             torch::Tensor index,
                                             long dim_size) {
-  auto out = scatter_sum_fwd(src, index, dim_size);
+  auto acc = scatter_sum_acc(src, index, dim_size);
   long E = index.numel();
-  long F = E > 0 ? src.numel() / src.size(0) : 1;
+  long F = row_elems(src);
   auto count = torch::zeros({dim_size}, src.options().dtype(torch::kFloat));
-  auto idx = index.contiguous();
-  if (E > 0) {
-    hipLaunchKernelGGL(count_kernel, dim3(n_blocks(E, kBlock)), dim3(kBlock),
-                       0, cur_stream(), idx.data_ptr<long>(),
-                       count.data_ptr<float>(), E);
-    AT_DISPATCH_FLOATING_TYPES_AND2(
-        at::ScalarType::BFloat16, at::ScalarType::Half, out.scalar_type(),
-        "divide_rows", [&] {
-          hipLaunchKernelGGL(divide_rows_kernel<scalar_t>,
-                             dim3(n_blocks(dim_size * F, kBlock)),
-                             dim3(kBlock), 0, cur_stream(),
-                             out.data_ptr<scalar_t>(), count.data_ptr<float>(),
-                             dim_size, F);
-        });
+  if (E > 0 && dim_size > 0) {
+    auto idx = index.contiguous();
+    LAUNCH(count_kernel, E, 2048, idx.data_ptr<long>(),
+           count.data_ptr<float>(), E);
+    if (F > 0) {
+      // divide the accumulator; a half type is rounded once, after
+      AT_DISPATCH_FLOATING_TYPES(acc.scalar_type(), "divide_rows", [&] {
+        LAUNCH(divide_rows_kernel<scalar_t>, dim_size * F, 2048,
+               acc.data_ptr<scalar_t>(), count.data_ptr<float>(), dim_size,
+               F);
+      });
+    }
   }
-  return {out, count};
+  return {acc.to(src.scalar_type()), count};
 }
 
 std::vector<torch::Tensor> scatter_minmax_fwd_f64(torch::Tensor src,
@@ -546,7 +527,7 @@ std::vector<torch::Tensor> scatter_minmax_fwd_f64(torch::Tensor src,
                                                   bool is_max) {
   auto srcd = src.contiguous();
   long E = index.numel();
-  long F = E > 0 ? srcd.numel() / srcd.size(0) : 1;
+  long F = row_elems(srcd);
   auto sizes = src.sizes().vec();
   sizes[0] = dim_size;
   long total = dim_size * F;
@@ -560,30 +541,22 @@ std::vector<torch::Tensor> scatter_minmax_fwd_f64(torch::Tensor src,
                            : (raw | 0x8000000000000000ull);
     bits.fill_((long)u);
   }
-  auto arg64 = torch::full(sizes, (long)0x7fffffffffffffffLL,
+  auto arg64 = torch::full(sizes, (long)kNoArg,
                            src.options().dtype(torch::kLong));
   auto out = torch::empty(sizes, src.options());
   auto arg = torch::empty(sizes, src.options().dtype(torch::kLong));
-  if (E > 0) {
-    hipLaunchKernelGGL(scatter_max_pass1_f64, dim3(n_blocks(E * F, kBlock)),
-                       dim3(kBlock), 0, cur_stream(), srcd.data_ptr<double>(),
-                       idx.data_ptr<long>(),
-                       reinterpret_cast<unsigned long long*>(bits.data_ptr<long>()),
-                       E, F, is_max);
-    hipLaunchKernelGGL(scatter_max_pass2_f64, dim3(n_blocks(E * F, kBlock)),
-                       dim3(kBlock), 0, cur_stream(), srcd.data_ptr<double>(),
-                       idx.data_ptr<long>(),
-                       reinterpret_cast<unsigned long long*>(bits.data_ptr<long>()),
-                       reinterpret_cast<unsigned long long*>(arg64.data_ptr<long>()),
-                       E, F);
+  auto bits_p = reinterpret_cast<unsigned long long*>(bits.data_ptr<long>());
+  auto arg_p = reinterpret_cast<unsigned long long*>(arg64.data_ptr<long>());
+  if (E * F > 0 && dim_size > 0) {
+    LAUNCH(scatter_max_pass1_f64, E * F, 2048, srcd.data_ptr<double>(),
+           idx.data_ptr<long>(), bits_p, E, F, is_max);
+    LAUNCH(scatter_max_pass2_f64, E * F, 2048, srcd.data_ptr<double>(),
+           idx.data_ptr<long>(), bits_p, arg_p, E, F);
   }
-  hipLaunchKernelGGL(scatter_max_finalize_f64,
-                     dim3(n_blocks(total, kBlock)), dim3(kBlock), 0,
-                     cur_stream(),
-                     reinterpret_cast<unsigned long long*>(bits.data_ptr<long>()),
-                     reinterpret_cast<unsigned long long*>(arg64.data_ptr<long>()),
-                     out.data_ptr<double>(), arg.data_ptr<long>(), total,
-                     is_max);
+  if (total > 0) {
+    LAUNCH(scatter_max_finalize_f64, total, 2048, bits_p, arg_p,
+           out.data_ptr<double>(), arg.data_ptr<long>(), total);
+  }
   return {out, arg};
 }
 
@@ -591,12 +564,15 @@ std::vector<torch::Tensor> scatter_minmax_fwd(torch::Tensor src,
                                               torch::Tensor index,
                                               long dim_size, bool is_max) {
   CHECK_CUDA(src); CHECK_CUDA(index);
+  TORCH_CHECK(index.dtype() == torch::kLong);
+  TORCH_CHECK(src.dim() >= 1 && index.numel() == src.size(0),
+              "index must hold one entry per src row");
   if (src.scalar_type() == at::ScalarType::Double) {
     return scatter_minmax_fwd_f64(src, index, dim_size, is_max);
   }
   auto srcf = src.contiguous().to(torch::kFloat);
   long E = index.numel();
-  long F = E > 0 ? srcf.numel() / srcf.size(0) : 1;
+  long F = row_elems(srcf);
   auto sizes = src.sizes().vec();
   sizes[0] = dim_size;
   long total = dim_size * F;
@@ -611,29 +587,22 @@ std::vector<torch::Tensor> scatter_minmax_fwd(torch::Tensor src,
     u = (raw & 0x80000000u) ? ~raw : (raw | 0x80000000u);
     bits.fill_((int)u);
   }
-  auto arg64 = torch::full(sizes, (long)0x7fffffffffffffffLL,
+  auto arg64 = torch::full(sizes, (long)kNoArg,
                            src.options().dtype(torch::kLong));
   auto out = torch::empty(sizes, src.options().dtype(torch::kFloat));
   auto arg = torch::empty(sizes, src.options().dtype(torch::kLong));
-  if (E > 0) {
-    hipLaunchKernelGGL(scatter_max_pass1, dim3(n_blocks(E * F, kBlock)),
-                       dim3(kBlock), 0, cur_stream(), srcf.data_ptr<float>(),
-                       idx.data_ptr<long>(),
-                       reinterpret_cast<unsigned int*>(bits.data_ptr<int>()),
-                       E, F, is_max);
-    hipLaunchKernelGGL(scatter_max_pass2, dim3(n_blocks(E * F, kBlock)),
-                       dim3(kBlock), 0, cur_stream(), srcf.data_ptr<float>(),
-                       idx.data_ptr<long>(),
-                       reinterpret_cast<unsigned int*>(bits.data_ptr<int>()),
-                       reinterpret_cast<unsigned long long*>(arg64.data_ptr<long>()),
-                       E, F);
+  auto bits_p = reinterpret_cast<unsigned int*>(bits.data_ptr<int>());
+  auto arg_p = reinterpret_cast<unsigned long long*>(arg64.data_ptr<long>());
+  if (E * F > 0 && dim_size > 0) {
+    LAUNCH(scatter_max_pass1, E * F, 2048, srcf.data_ptr<float>(),
+           idx.data_ptr<long>(), bits_p, E, F, is_max);
+    LAUNCH(scatter_max_pass2, E * F, 2048, srcf.data_ptr<float>(),
+           idx.data_ptr<long>(), bits_p, arg_p, E, F);
   }
-  hipLaunchKernelGGL(scatter_max_finalize, dim3(n_blocks(total, kBlock)),
-                     dim3(kBlock), 0, cur_stream(),
-                     reinterpret_cast<unsigned int*>(bits.data_ptr<int>()),
-                     reinterpret_cast<unsigned long long*>(arg64.data_ptr<long>()),
-                     out.data_ptr<float>(), arg.data_ptr<long>(), total,
-                     is_max);
+  if (total > 0) {
+    LAUNCH(scatter_max_finalize, total, 2048, bits_p, arg_p,
+           out.data_ptr<float>(), arg.data_ptr<long>(), total);
+  }
   return {out.to(src.scalar_type()), arg};
 }
 
@@ -646,10 +615,11 @@ std::vector<torch::Tensor> radius_pairs(torch::Tensor pos, torch::Tensor batch,
   auto count = torch::zeros({N}, pos.options().dtype(torch::kInt));
   auto b = batch.contiguous();
   auto gp = gptr.contiguous();
-  hipLaunchKernelGGL(radius_count_kernel, dim3(n_blocks(N, kBlock)),
-                     dim3(kBlock), 0, cur_stream(), pos.data_ptr<float>(),
-                     b.data_ptr<long>(), gp.data_ptr<long>(), N, r2, loop,
-                     count.data_ptr<int>());
+  if (N > 0) {
+    LAUNCH(radius_count_kernel, N, 2048, pos.data_ptr<float>(),
+           b.data_ptr<long>(), gp.data_ptr<long>(), N, r2, loop,
+           count.data_ptr<int>());
+  }
   auto offs = torch::zeros({N}, pos.options().dtype(torch::kLong));
   auto csum = count.to(torch::kLong).cumsum(0);
   offs.slice(0, 1, N).copy_(csum.slice(0, 0, N - 1));
@@ -658,12 +628,10 @@ std::vector<torch::Tensor> radius_pairs(torch::Tensor pos, torch::Tensor batch,
   auto dst = torch::empty({E}, pos.options().dtype(torch::kLong));
   auto dist = torch::empty({E}, pos.options().dtype(torch::kFloat));
   if (E > 0) {
-    hipLaunchKernelGGL(radius_fill_kernel, dim3(n_blocks(N, kBlock)),
-                       dim3(kBlock), 0, cur_stream(), pos.data_ptr<float>(),
-                       b.data_ptr<long>(), gp.data_ptr<long>(),
-                       offs.data_ptr<long>(), N, r2, loop,
-                       src.data_ptr<long>(), dst.data_ptr<long>(),
-                       dist.data_ptr<float>());
+    LAUNCH(radius_fill_kernel, N, 2048, pos.data_ptr<float>(),
+           b.data_ptr<long>(), gp.data_ptr<long>(), offs.data_ptr<long>(), N,
+           r2, loop, src.data_ptr<long>(), dst.data_ptr<long>(),
+           dist.data_ptr<float>());
   }
   return {src, dst, dist};
 }
@@ -787,7 +755,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scatter_sum_fwd", &scatter_sum_fwd, "scatter-add (HIP)");
   m.def("segment_sum_csr", &segment_sum_csr, "CSR segment sum (HIP)",
         pybind11::arg("src"), pybind11::arg("rowptr"),
-        pybind11::arg("perm") = pybind11::none());
+        pybind11::arg("perm") = pybind11::none(),
+        pybind11::arg("mean") = false);
   m.def("scatter_mean_fwd", &scatter_mean_fwd, "scatter-mean (HIP)");
   m.def("scatter_minmax_fwd", &scatter_minmax_fwd, "scatter-min/max (HIP)");
   m.def("radius_pairs", &radius_pairs, "radius pair enumeration (HIP)");

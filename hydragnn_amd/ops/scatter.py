@@ -134,12 +134,13 @@ class _ScatterMean(torch.autograd.Function):
             ext = get_extension(required=True)
             if sorted_index and \
                     os.environ.get("HYDRAGNN_CSR_SCATTER", "1") == "1":
-                # contention-free: CSR sum + rowptr-derived counts
+                # contention-free: CSR sum + rowptr-derived counts; the
+                # kernel divides its accumulator (fp32 for bf16/f16) by
+                # the row length before the one store
                 rowptr = _rowptr_from_sorted(index, dim_size)
                 count = (rowptr[1:] - rowptr[:-1]).to(src.dtype)
-                s = ext.segment_sum_csr(src.contiguous(), rowptr)
-                out = s / count.clamp(min=1).view(
-                    -1, *([1] * (src.dim() - 1)))
+                out = ext.segment_sum_csr(src.contiguous(), rowptr,
+                                          None, True)
                 ctx.save_for_backward(index, count)
                 return out
             out, count = ext.scatter_mean_fwd(src.contiguous(), index, dim_size)
@@ -180,27 +181,20 @@ class _ScatterMax(torch.autograd.Function):
             out = torch.where(
                 present.view(-1, *([1] * (src.dim() - 1))),
                 out, torch.zeros_like(out))
-            # argmax for backward
-            gathered = out.index_select(0, index)
-            is_arg = (gathered == src)
-            eidx = torch.arange(src.shape[0], device=src.device)
+            # arg for backward: the lowest edge index attaining the
+            # extreme wins (amin over the matching edges; E = no match)
+            n_edges = src.shape[0]
+            idx_e = index.view(-1, *([1] * (src.dim() - 1))).expand_as(src)
+            eidx = torch.arange(n_edges, device=src.device).view(
+                -1, *([1] * (src.dim() - 1))).expand_as(src)
+            cand = torch.where(out.index_select(0, index) == src, eidx,
+                               torch.full_like(eidx, n_edges))
             arg = torch.full(
-                (dim_size,) + src.shape[1:], -1, dtype=torch.long,
+                (dim_size,) + src.shape[1:], n_edges, dtype=torch.long,
                 device=src.device)
-            # first matching edge wins (reverse order so lowest index wins)
-            flip = torch.flip(eidx, [0])
-            src_f = src.flip(0)
-            idx_f = index.flip(0)
-            ga = out.index_select(0, idx_f)
-            m = ga == src_f
-            arg_src = torch.where(
-                m, flip.view(-1, *([1] * (src.dim() - 1))).expand_as(src),
-                torch.full_like(src, -1, dtype=torch.long)
-                if src.dtype == torch.long else
-                torch.full(src.shape, -1, dtype=torch.long, device=src.device))
-            arg = arg.scatter_reduce(
-                0, idx_f.view(-1, *([1] * (src.dim() - 1))).expand_as(arg_src),
-                arg_src, "amax", include_self=True)
+            arg = arg.scatter_reduce(0, idx_e, cand, "amin",
+                                     include_self=True)
+            arg = torch.where(arg == n_edges, torch.full_like(arg, -1), arg)
         ctx.save_for_backward(arg)
         ctx.src_shape = src.shape
         return out
@@ -209,6 +203,9 @@ class _ScatterMax(torch.autograd.Function):
     def backward(ctx, grad_out):
         (arg,) = ctx.saved_tensors
         grad_src = grad_out.new_zeros(ctx.src_shape)
+        if grad_src.numel() == 0:
+            # no edges: every arg is -1 and there is no row to index
+            return grad_src, None, None, None
         valid = arg >= 0
         flat_arg = arg.clamp(min=0)
         grad_src.scatter_add_(

@@ -306,8 +306,10 @@ class EquivariantProductBasisBlock(nn.Module):
         self.linear = IrrepsLinear(num_channels, num_channels, lmax_out)
 
     def forward(self, node_feats: torch.Tensor, node_elem: torch.Tensor,
-                sc: Optional[torch.Tensor] = None) -> torch.Tensor:
-        out = self.symmetric_contractions(node_feats, node_elem)
+                sc: Optional[torch.Tensor] = None,
+                elem_csr=None) -> torch.Tensor:
+        out = self.symmetric_contractions(node_feats, node_elem,
+                                          elem_csr=elem_csr)
         want = self.linear.lmap.numel()
         add = sc[:, :, :want] if sc is not None else None
         return self.linear(out, add=add)

@@ -186,6 +186,13 @@ class MACEStack(Base):
         n_graphs = data.get("num_graphs_")
         n_graphs = int(n_graphs) if n_graphs is not None else \
             int(batch.max()) + 1
+        # nodes sorted by element, once per batch: every product
+        # block's fused contraction sums its weight gradients over it
+        elem_csr = None
+        from ...ops import symcon as _symcon
+        if h0.is_cuda and len(self.products) > 0 and _symcon.enabled():
+            elem_csr = self.products[0].symmetric_contractions \
+                .element_sort(elem)
 
         head_outputs = [None] * self.num_heads
         for ilayer, (inter, prod) in enumerate(
@@ -200,7 +207,7 @@ class MACEStack(Base):
                           edges_sorted=bool(data.get("edges_sorted_",
                                                      False)),
                           etp_meta=etp_meta)
-            node_feats = prod(m, elem, sc=sc)
+            node_feats = prod(m, elem, sc=sc, elem_csr=elem_csr)
             for ihead in range(self.num_heads):
                 r = self.readouts[ihead][ilayer](node_feats)
                 head_outputs[ihead] = r if head_outputs[ihead] is None \

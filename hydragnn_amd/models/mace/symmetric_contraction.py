@@ -166,8 +166,34 @@ class SymmetricContraction(nn.Module):
             Contraction(lmax_in, lout, correlation, num_channels,
                         num_elements)
             for lout in range(lmax_out + 1)])
+        self.num_elements = num_elements
+        self._table = None  # ops.symcon.SymconTable, built on first use
 
-    def forward(self, x: torch.Tensor, node_elem: torch.Tensor
-                ) -> torch.Tensor:
+    def symcon_table(self):
+        """The block as one polynomial table (ops/symcon.py), expanded
+        from the U buffers once per module."""
+        if self._table is None:
+            from ...ops.symcon import table_from_contractions
+            self._table = table_from_contractions(self.contractions)
+        return self._table
+
+    def element_sort(self, node_elem: torch.Tensor):
+        """Nodes sorted by element, for the fused op's weight-gradient
+        sums; a stack builds it once per batch for all its blocks."""
+        from ...ops.symcon import element_sort
+        return element_sort(node_elem, self.num_elements)
+
+    def forward(self, x: torch.Tensor, node_elem: torch.Tensor,
+                elem_csr=None) -> torch.Tensor:
+        """x [N, C, D]; node_elem [N] -> [N, C, dim(lmax_out)].  One
+        fused launch per pass where ops/symcon.py's kernels apply
+        (`HYDRAGNN_SYMCON=0` switches them off), else the per-lout
+        composition below."""
+        if x.is_cuda:
+            from ...ops import symcon as sc
+            table = self.symcon_table()
+            if sc.enabled() and sc.kernel_ok(table, x):
+                W = sc.concat_weights(self.contractions, x.dtype)
+                return sc.symcon(x, W, node_elem, table, elem_csr)
         outs = [c(x, node_elem) for c in self.contractions]
         return torch.cat(outs, dim=-1)  # [N, C, dim(lmax_out)]

@@ -711,8 +711,35 @@ std::vector<torch::Tensor> radius_pairs_cells(
     torch::Tensor pos, torch::Tensor order, torch::Tensor cell_of,
     torch::Tensor cell_start, long ncx, long ncy, long ncz, double r,
     bool loop);
+// defined in symcon.hip
+torch::Tensor symcon_forward(torch::Tensor x, torch::Tensor elem,
+                             torch::Tensor W, torch::Tensor ent,
+                             torch::Tensor coef, long Do);
+std::vector<torch::Tensor> symcon_grad(
+    torch::Tensor x, torch::Tensor g, c10::optional<torch::Tensor> t,
+    torch::Tensor W, torch::Tensor perm, torch::Tensor rowptr,
+    torch::Tensor ent, torch::Tensor coef, long mask);
+long symcon_lds_bytes(long D, long Do, long P, long K, long order,
+                      long acc_bytes);
+std::vector<long> symcon_grad_geometry(long N, long C, long D, long Do,
+                                       long P, long K, long order,
+                                       long nel, bool dbl);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("symcon_forward", &symcon_forward,
+        "fused symmetric contraction, whole output tower (HIP)");
+  m.def("symcon_grad", &symcon_grad,
+        "symmetric contraction first order (t None) or second order "
+        "(HIP); mask bits: 1 x, 2 W, 4 g",
+        pybind11::arg("x"), pybind11::arg("g"), pybind11::arg("t"),
+        pybind11::arg("W"), pybind11::arg("perm"),
+        pybind11::arg("rowptr"), pybind11::arg("ent"),
+        pybind11::arg("coef"), pybind11::arg("mask"));
+  m.def("symcon_lds_bytes", &symcon_lds_bytes,
+        "dynamic-LDS bytes of a symcon launch (order 0 = forward)");
+  m.def("symcon_grad_geometry", &symcon_grad_geometry,
+        "(block, channel tile, row lanes, Z, channel tiles) of a "
+        "symcon_grad launch");
   m.def("etp_general", &etp_general, "fused ETP contraction (HIP)",
         pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("C"),
         pybind11::arg("entries"), pybind11::arg("coefs"),

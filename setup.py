@@ -16,7 +16,8 @@ ext_modules = [
                  "hydragnn_amd/ops/csrc/gemv.hip",
                  "hydragnn_amd/ops/csrc/radius.hip",
                  "hydragnn_amd/ops/csrc/fused_adamw.hip",
-                 "hydragnn_amd/ops/csrc/irreps_linear.hip"],
+                 "hydragnn_amd/ops/csrc/irreps_linear.hip",
+                 "hydragnn_amd/ops/csrc/symcon.hip"],
         extra_compile_args={
             "cxx": ["-O3"],
             "nvcc": ["-O3", "--offload-arch=gfx950"],

@@ -10,13 +10,24 @@ On MI355X the multihead path runs the segment-varlen HIP kernels
 (ops/csrc/varlen_attn.hip), forward and first-order backward: one
 (graph, head) workgroup with the other side tiled through LDS, over
 exactly the graph's nodes — no dense padding, fp32 or bf16, graphs of
-any size.  Heads wider than 128 and the Performer path fall back to
-dense-batch SDPA.
+any size.  Heads wider than 128 fall back to dense-batch SDPA.
+
+The Performer path runs on the segment linear-attention primitives
+(ops/segment_linear.py, ops/csrc/segment_linear.hip):
+``PerformerAttention.forward_segments`` is the dense forward term for
+term on the un-padded rows -- K = segment_outer_sum(phi(k), [v, 1]),
+o = segment_matvec(phi(q), K), out = o[..., :d] / (o[..., d:] + 1e-6) --
+with no padding and no boolean un-padding, and differentiable to every
+order on the device because each primitive's gradients are the other
+primitive.  CPU tensors, widths outside the kernels' envelope (more than
+128 features or head_dim above 131) and HYDRAGNN_VARLEN_PERFORMER=0 keep
+the dense-batch einsum path.
 """
 
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -84,6 +95,24 @@ class PerformerAttention(nn.Module):
         out = out.transpose(1, 2).reshape(B, N, C)
         return self.out(out)
 
+    def forward_segments(self, x: torch.Tensor, ptr: torch.Tensor,
+                         batch: torch.Tensor):
+        """The same attention on un-padded rows: x [N, C], graph rowptr
+        [G+1], per-row graph index [N] -> [N, C].  The appended ones
+        column makes the last column of K the key sum, so one matvec
+        yields numerator and normaliser."""
+        from ..ops.segment_linear import segment_matvec, segment_outer_sum
+        N = x.shape[0]
+        H, d = self.heads, self.head_dim
+        q, k, v = self.qkv(x).view(N, 3, H, d).unbind(dim=1)
+        qp = self._phi(q)
+        kp = self._phi(k)
+        v1 = torch.cat([v, v.new_ones(N, H, 1)], dim=-1)
+        kv = segment_outer_sum(kp, v1, ptr, batch)
+        o = segment_matvec(qp, kv, ptr, batch)
+        out = o[..., :d] / (o[..., d:] + 1e-6)
+        return self.out(out.reshape(N, H * d))
+
 
 class HydraGPSConv(nn.Module):
     """Local MPNN + global attention + MLP with residuals/norms, on the
@@ -149,6 +178,25 @@ class HydraGPSConv(nn.Module):
         out = varlen_attention(q, k, v, ptr, batch)
         return attn.out_proj(out.reshape(x.shape[0], self.channels))
 
+    def _try_segment_performer(self, x, batch):
+        """Performer attention through the segment linear-attention HIP
+        kernels (no dense padding).  Returns None on the CPU, outside
+        the kernels' envelope or with HYDRAGNN_VARLEN_PERFORMER=0; the
+        caller then takes the dense-batch path."""
+        if os.environ.get("HYDRAGNN_VARLEN_PERFORMER", "1") == "0":
+            return None
+        if not x.is_cuda:
+            return None
+        from ..ops.scatter import _rowptr_from_sorted
+        from ..ops.segment_linear import segment_linear_ok
+        attn = self.attn
+        if not segment_linear_ok(attn.num_features, attn.head_dim + 1,
+                                 attn.projection):
+            return None
+        num_graphs = int(batch[-1]) + 1 if batch.numel() else 0
+        ptr = _rowptr_from_sorted(batch, num_graphs)
+        return attn.forward_segments(x, ptr, batch)
+
     def forward(self, inv_node_feat, equiv_node_feat, batch=None, **kwargs):
         hs = []
         equiv_out = equiv_node_feat
@@ -167,6 +215,8 @@ class HydraGPSConv(nn.Module):
         h_attn = None
         if self.attn_type == "multihead" and batch is not None:
             h_attn = self._try_varlen_attention(inv_node_feat, batch)
+        elif self.attn_type == "performer" and batch is not None:
+            h_attn = self._try_segment_performer(inv_node_feat, batch)
         if h_attn is None:
             x_dense, mask = to_dense_batch(inv_node_feat, batch)
             if self.attn_type == "multihead":

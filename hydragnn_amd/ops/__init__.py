@@ -24,6 +24,7 @@ from .basis import (
 from ._extension import has_extension, get_extension
 from .irreps_linear import irreps_linear
 from .varlen_attn import varlen_attention
+from .segment_linear import segment_outer_sum, segment_matvec
 from .mfma_linear import MFMALinear
 from .splitk_linear import SplitKLinear
 
@@ -35,4 +36,5 @@ __all__ = [
     "polynomial_cutoff", "cosine_cutoff",
     "has_extension", "get_extension",
     "irreps_linear", "varlen_attention", "MFMALinear", "SplitKLinear",
+    "segment_outer_sum", "segment_matvec",
 ]

@@ -725,7 +725,34 @@ std::vector<long> symcon_grad_geometry(long N, long C, long D, long Do,
                                        long P, long K, long order,
                                        long nel, bool dbl);
 
+// defined in segment_linear.hip
+torch::Tensor segment_outer_sum(torch::Tensor A, torch::Tensor B,
+                                torch::Tensor ptr, long z);
+torch::Tensor segment_matvec(torch::Tensor A, torch::Tensor K,
+                             torch::Tensor ptr, bool trans);
+long segment_linear_lds_bytes(long a, long b, at::ScalarType dtype,
+                              long pass);
+std::vector<long> segment_linear_tiling(long a, long b,
+                                        at::ScalarType dtype);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("segment_outer_sum", &segment_outer_sum,
+        "per-segment outer-product sum -> K[G, H, a, b] in the "
+        "accumulator type (HIP); z <= 0 picks the row split",
+        pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("ptr"),
+        pybind11::arg("z") = 0);
+  m.def("segment_matvec", &segment_matvec,
+        "per-row product with the row's segment matrix (HIP)",
+        pybind11::arg("A"), pybind11::arg("K"), pybind11::arg("ptr"),
+        pybind11::arg("trans") = false);
+  m.def("segment_linear_lds_bytes", &segment_linear_lds_bytes,
+        "dynamic-LDS bytes of a segment-linear launch "
+        "(pass 0 outer sum, 1 matvec, 2 matvec trans)",
+        pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("dtype"),
+        pybind11::arg("pass"));
+  m.def("segment_linear_tiling", &segment_linear_tiling,
+        "(outer-sum row tile R, matvec rows per workgroup pass)",
+        pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("dtype"));
   m.def("symcon_forward", &symcon_forward,
         "fused symmetric contraction, whole output tower (HIP)");
   m.def("symcon_grad", &symcon_grad,

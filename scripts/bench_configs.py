@@ -89,6 +89,22 @@ CONFIGS = {
                    global_attn_engine="gps",
                    global_attn_type="multihead", global_attn_heads=4,
                    activation_function="silu")),
+    "egnn_gps_performer": dict(
+        label="EGNN + GPS Performer attention, OC20-shape, bf16",
+        precision="bf16", local_batch=32, mlip=False,
+        data=lambda b: oc20_shape(b, with_pe=True),
+        model=dict(mpnn_type="EGNN", input_dim=1, hidden_dim=64,
+                   output_dim=[1], output_type=["graph"],
+                   output_heads={"graph": [{
+                       "type": "branch-0", "architecture": {
+                           "num_sharedlayers": 1, "dim_sharedlayers": 64,
+                           "num_headlayers": 2,
+                           "dim_headlayers": [64, 64]}}]},
+                   task_weights=[1.0], num_conv_layers=3, radius=4.0,
+                   max_neighbours=30, equivariance=True, pe_dim=3,
+                   global_attn_engine="gps",
+                   global_attn_type="performer", global_attn_heads=4,
+                   activation_function="silu")),
     "dimenet_fp64": dict(
         label="DimeNet fp64 + grad checkpointing, periodic cells",
         precision="fp64", local_batch=4, mlip=False,

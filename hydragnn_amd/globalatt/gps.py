@@ -7,7 +7,7 @@ residuals and three norms; Performer projection redraw is driven by the
 training loop, not forward (safe under activation checkpointing).
 
 On MI355X the multihead path runs the segment-varlen HIP kernels
-(ops/csrc/varlen_attn.hip), forward and first-order backward: one
+(ops/csrc/varlen_attn.hip), forward, first- and second-order backward: one
 (graph, head) workgroup with the other side tiled through LDS, over
 exactly the graph's nodes — no dense padding, fp32 or bf16, graphs of
 any size.  Heads wider than 128 fall back to dense-batch SDPA.

@@ -679,6 +679,11 @@ std::vector<torch::Tensor> varlen_attention_bwd(
     torch::Tensor LSE, torch::Tensor dO, torch::Tensor ptr);
 long varlen_attention_lds_bytes(long dh, long pass);
 std::vector<long> varlen_attention_tiling(long dh);
+std::vector<torch::Tensor> varlen_attention_bwd2(
+    torch::Tensor Q, torch::Tensor K, torch::Tensor V, torch::Tensor O,
+    torch::Tensor LSE, torch::Tensor dO, torch::Tensor cQ,
+    torch::Tensor cK, torch::Tensor cV, torch::Tensor ptr);
+std::vector<long> varlen_attention_tiling2(long dh);
 
 // defined in irreps_linear.hip
 torch::Tensor irreps_linear(torch::Tensor X, torch::Tensor W,
@@ -834,10 +839,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "segment-varlen attention backward -> (dQ, dK, dV) (HIP)");
   m.def("varlen_attention_lds_bytes", &varlen_attention_lds_bytes,
         "LDS bytes of a varlen-attention instance "
-        "(pass 0 fwd, 1 dQ, 2 dK/dV)",
+        "(pass 0 fwd, 1 dQ, 2 dK/dV, 3 and 4 second order)",
         pybind11::arg("dh"), pybind11::arg("pass"));
   m.def("varlen_attention_tiling", &varlen_attention_tiling,
         "(tile rows, rows per workgroup pass) of the instance for dh");
+  m.def("varlen_attention_bwd2", &varlen_attention_bwd2,
+        "segment-varlen attention second order -> (gQ, gK, gV, gdO) "
+        "(HIP)");
+  m.def("varlen_attention_tiling2", &varlen_attention_tiling2,
+        "(tile rows, rows per workgroup pass) of the second-order "
+        "instance for dh");
   m.def("irreps_linear", &irreps_linear,
         "per-l channel-mixing MFMA linear (HIP)",
         pybind11::arg("X"), pybind11::arg("W"), pybind11::arg("lmap"),

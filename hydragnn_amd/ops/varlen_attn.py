@@ -14,14 +14,19 @@ Orders of differentiation:
 * first order: ``varlen_attention_bwd``, two atomic-free passes that
   recompute P from LSE (``_VarlenAttnBwd.forward``) -- no host sync, no
   dense re-padding;
-* second order (force-style training): ``_VarlenAttnBwd.backward``
-  recomputes the attention through a pure-torch reference (dense-batch
-  explicit softmax with a finite mask bias, query-chunked above 1024
-  nodes per segment) and differentiates that twice.
+* second order (force-style training): ``varlen_attention_bwd2``, two
+  more atomic-free passes (``_VarlenAttnBwd.backward`` with grad mode
+  off, the ordinary ``loss.backward()``) -- no host sync either, so the
+  whole step captures into a device graph;
+* third order, or ``HYDRAGNN_VARLEN_ATTN_BWD2=0``:
+  ``_VarlenAttnBwd.backward`` recomputes the attention through a
+  pure-torch reference (dense-batch explicit softmax with a finite mask
+  bias, query-chunked above 1024 nodes per segment; syncs on the segment
+  sizes) and differentiates that twice.
 
 ``HYDRAGNN_VARLEN_ATTN_BWD=0`` restores the first-order recompute
 backward (the torch reference differentiated once).  On CPU tensors the
-same two autograd Functions run on pure-torch doubles of the two entry
+same two autograd Functions run on pure-torch doubles of the three entry
 points, which is what the autograd-closure tests check without a GPU.
 """
 
@@ -129,6 +134,51 @@ def torch_varlen_attention_bwd(q, k, v, out, lse, dout, ptr):
     return dq, dk, dv
 
 
+def torch_varlen_attention_bwd2(q, k, v, out, lse, dout, cq, ck, cv, ptr):
+    """Pure-torch double of the ``varlen_attention_bwd2`` entry point:
+    the gradients of R = <cq, dQ> + <ck, dK> + <cv, dV> with respect to
+    (q, k, v, dO), where (dQ, dK, dV) = varlen_attention_bwd(...) and
+    ``out``/``lse`` are functions of (q, k, v) that get no gradient of
+    their own.  A cotangent given as None is zero.  Per segment, with
+    s = scale q k^T, P = exp(s - LSE), a = dO V^T, D = rowsum(dO * O),
+    T = scale (cq k^T + q ck^T), W = dO cv^T:
+
+        t = rowsum(P T), u = rowsum(P T a), w = rowsum(P W),
+        e = u - 2 t D + w,
+        E = (T - t) a - D T + W,  GS = P (E - e),  dS = P (a - D),
+        g_dO = P (T - t) V + P cv,        g_v = (P (T - t))^T dO,
+        g_q = scale (GS K + dS ck),       g_k = scale (GS^T Q + dS^T cq).
+    """
+    N, H, dh = q.shape
+    scale = 1.0 / math.sqrt(dh)
+    cq, ck, cv = (torch.zeros_like(q) if c is None else c
+                  for c in (cq, ck, cv))
+    gq, gk, gv, gg = (torch.empty_like(q) for _ in range(4))
+    for lo, hi in _segments(ptr):
+        qg, kg, vg, og, dg, cqg, ckg, cvg = (
+            t[lo:hi].transpose(0, 1)
+            for t in (q, k, v, out, dout, cq, ck, cv))
+        kt = kg.transpose(-1, -2)
+        p = torch.exp(qg @ kt * scale
+                      - lse[lo:hi].transpose(0, 1)[..., None].to(q.dtype))
+        a = dg @ vg.transpose(-1, -2)
+        d = (dg * og).sum(-1, keepdim=True)
+        tt = (cqg @ kt + qg @ ckg.transpose(-1, -2)) * scale
+        w = dg @ cvg.transpose(-1, -2)
+        t = (p * tt).sum(-1, keepdim=True)
+        e = (p * tt * a).sum(-1, keepdim=True) - 2 * t * d \
+            + (p * w).sum(-1, keepdim=True)
+        ptc = p * (tt - t)
+        gs = p * ((tt - t) * a - d * tt + w - e)
+        ds = p * (a - d)
+        gg[lo:hi] = (ptc @ vg + p @ cvg).transpose(0, 1)
+        gv[lo:hi] = (ptc.transpose(-1, -2) @ dg).transpose(0, 1)
+        gq[lo:hi] = (gs @ kg + ds @ ckg).transpose(0, 1) * scale
+        gk[lo:hi] = (gs.transpose(-1, -2) @ qg
+                     + ds.transpose(-1, -2) @ cqg).transpose(0, 1) * scale
+    return gq, gk, gv, gg
+
+
 def varlen_tiling(head_dim: int):
     """(tile rows T, rows per workgroup pass B) of the kernel instance
     that serves ``head_dim``."""
@@ -136,8 +186,18 @@ def varlen_tiling(head_dim: int):
     return t, b
 
 
+def varlen_tiling2(head_dim: int):
+    """The same for the second-order instance that serves ``head_dim``."""
+    t, b = get_extension(required=True).varlen_attention_tiling2(head_dim)
+    return t, b
+
+
 def _kernel_backward_enabled() -> bool:
     return os.environ.get("HYDRAGNN_VARLEN_ATTN_BWD", "1") != "0"
+
+
+def _kernel_second_order_enabled() -> bool:
+    return os.environ.get("HYDRAGNN_VARLEN_ATTN_BWD2", "1") != "0"
 
 
 def _recompute_out(q, k, v, batch):
@@ -161,10 +221,17 @@ class _VarlenAttn(torch.autograd.Function):
         else:
             out, lse = torch_varlen_attention_fwd(q, k, v, ptr)
         ctx.save_for_backward(q, k, v, out, lse, ptr, batch)
+        ctx.set_materialize_grads(False)
         return out
 
     @staticmethod
     def backward(ctx, g):
+        # the double backward reaches this node a second time through
+        # the saved ``out``, which gets no gradient there: without this
+        # the engine would hand in zeros and the first-order kernels
+        # would run once more for nothing
+        if g is None:
+            return (None,) * 5
         q, k, v, out, lse, ptr, batch = ctx.saved_tensors
         if _kernel_backward_enabled():
             dq, dk, dv = _VarlenAttnBwd.apply(
@@ -185,8 +252,11 @@ class _VarlenAttn(torch.autograd.Function):
 
 
 class _VarlenAttnBwd(torch.autograd.Function):
-    """(q, k, v, out, lse, g) -> (dq, dk, dv) on the backward kernels;
-    its own backward (the double backward) is torch ops."""
+    """(q, k, v, out, lse, g) -> (dq, dk, dv) on the backward kernels.
+    Its own backward (the double backward) runs the second-order
+    kernels when no third order is requested (grad mode off, the
+    ordinary ``loss.backward()`` of force training), and the torch
+    recompute otherwise."""
 
     @staticmethod
     def forward(ctx, q, k, v, out, lse, g, ptr, batch):
@@ -198,22 +268,44 @@ class _VarlenAttnBwd(torch.autograd.Function):
         else:
             dq, dk, dv = torch_varlen_attention_bwd(
                 q, k, v, out, lse, g, ptr)
-        ctx.save_for_backward(q, k, v, g, batch)
+        ctx.save_for_backward(q, k, v, g, batch, out, lse, ptr)
         ctx.set_materialize_grads(False)
         return dq, dk, dv
 
     @staticmethod
+    def _kernel_route(q) -> bool:
+        if torch.is_grad_enabled() or not _kernel_second_order_enabled():
+            return False
+        return not q.is_cuda or q.dtype in (torch.float32, torch.bfloat16)
+
+    @staticmethod
     def backward(ctx, *cots):
+        if all(c is None for c in cots):
+            return (None,) * 8
+        if _VarlenAttnBwd._kernel_route(ctx.saved_tensors[0]):
+            # out and lse are functions of (q, k, v) and get no gradient
+            # of their own, as below; an absent cotangent is a zero
+            # tensor, so the kernels carry no optional operands
+            q, k, v, g, _, out, lse, ptr = ctx.saved_tensors
+            cq, ck, cv = (torch.zeros_like(q) if c is None
+                          else c.contiguous() for c in cots)
+            if q.is_cuda:
+                ext = get_extension(required=True)
+                gq, gk, gv, gg = ext.varlen_attention_bwd2(
+                    q.contiguous(), k.contiguous(), v.contiguous(), out,
+                    lse, g, cq, ck, cv, ptr)
+            else:
+                gq, gk, gv, gg = torch_varlen_attention_bwd2(
+                    q, k, v, out, lse, g, cq, ck, cv, ptr)
+            return gq, gk, gv, None, None, gg, None, None
         # out and lse are functions of (q, k, v): the recompute below
         # carries that dependence, so they get no gradient of their own.
         # The cotangent g enters as a fresh leaf -- its own history
         # (e.g. g = 2 * out) is differentiated by the caller's graph
         # from the gradient returned for it here, not a second time
         # inside this recompute.
-        *qkv, g, batch = ctx.saved_tensors
+        *qkv, g, batch = ctx.saved_tensors[:5]
         pairs = [(i, c) for i, c in enumerate(cots) if c is not None]
-        if not pairs:
-            return (None,) * 8
         with torch.enable_grad():
             g = g.detach().requires_grad_(True)
             # an operand outside the caller's graph still has to be
@@ -245,7 +337,8 @@ def varlen_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                      ptr: torch.Tensor, batch: torch.Tensor):
     """[N, H, dh] q/k/v, graph rowptr [G+1] and per-node graph index
     [N] -> [N, H, dh].  HIP kernels on GPU (fp32 or bf16, head_dim <=
-    128, forward and first-order backward), torch reference on CPU."""
+    128, forward, first- and second-order backward), torch reference on
+    CPU."""
     if not q.is_cuda:
         return torch_varlen_attention(q, k, v, batch)
     return varlen_attention_fn(q, k, v, ptr, batch)

@@ -682,8 +682,25 @@ __global__ void etp_sweep_kernel(
 
 }  // namespace
 
+// defined in etp_static.hip
+bool etp_static_launch(long table_id, int order, int omask, int tmask,
+                       at::ScalarType dtype, long rows, int nch, int da,
+                       int db, int dg, int do_, const void* const prim[4],
+                       const void* const tang[4], void* const outs[4],
+                       bool vec);
+void etp_count_generic();
+
 static hipStream_t etp_stream() {
   return at::hip::getCurrentHIPStream().stream();
+}
+
+// HYDRAGNN_ETP_SWEEP_VEC=0 keeps element-wise row accesses (A/B aid)
+static bool etp_sweep_vec() {
+  static bool v = []() {
+    const char* e = getenv("HYDRAGNN_ETP_SWEEP_VEC");
+    return !(e && e[0] == '0');
+  }();
+  return v;
 }
 
 static int etp_block_size() {
@@ -716,7 +733,7 @@ torch::Tensor etp_general(torch::Tensor A, torch::Tensor B, torch::Tensor C,
                           c10::optional<torch::Tensor> ai,
                           c10::optional<torch::Tensor> bi,
                           c10::optional<torch::Tensor> ci,
-                          long n_rows) {
+                          long n_rows, long static_id) {
   TORCH_CHECK(A.is_cuda() && A.is_contiguous());
   TORCH_CHECK(B.is_contiguous() && C.is_contiguous());
   long E = n_rows > 0 ? n_rows : A.size(0);
@@ -727,6 +744,25 @@ torch::Tensor etp_general(torch::Tensor A, torch::Tensor B, torch::Tensor C,
               "etp dims exceed kernel limits");
   auto out = torch::empty({E, A.size(1), do_}, A.options());
   if (NC == 0) return out;
+  if (static_id >= 0 && !ai.has_value() && !bi.has_value() &&
+      !ci.has_value() && E == A.size(0) && B.size(0) == E &&
+      C.size(0) == E && C.size(1) == nch &&
+      B.scalar_type() == A.scalar_type() &&
+      C.scalar_type() == A.scalar_type()) {
+    // compile-time table (etp_static.hip): registers only, no LDS
+    const void* prim[4] = {A.data_ptr(), B.data_ptr(), C.data_ptr(),
+                           nullptr};
+    const void* tang[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* outp[4] = {nullptr, nullptr, nullptr, out.data_ptr()};
+    bool vec = etp_sweep_vec();
+    for (const void* p : {prim[0], prim[1], prim[2],
+                          (const void*)outp[3]})
+      vec = vec && reinterpret_cast<uintptr_t>(p) % 16 == 0;
+    if (etp_static_launch(static_id, 0, 8, 0, A.scalar_type(), E, nch,
+                          da, db, dg, (int)do_, prim, tang, outp, vec))
+      return out;
+  }
+  etp_count_generic();
   int n_ent = entries.size(0);
   int block = etp_block_size();
   size_t accs = A.scalar_type() == at::ScalarType::Double ? 8 : 4;
@@ -884,15 +920,6 @@ torch::Tensor etp_reduce(torch::Tensor A, torch::Tensor C, torch::Tensor D,
 
 // ---- sweep family host side ----------------------------------------
 
-// HYDRAGNN_ETP_SWEEP_VEC=0 keeps element-wise row accesses (A/B aid)
-static bool etp_sweep_vec() {
-  static bool v = []() {
-    const char* e = getenv("HYDRAGNN_ETP_SWEEP_VEC");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
 static int etp_sweep_block_size() {
   static int b = []() {
     const char* e = getenv("HYDRAGNN_ETP_SWEEP_BLOCK");
@@ -921,7 +948,8 @@ std::vector<torch::Tensor> etp_sweep(
     torch::Tensor A, torch::Tensor B, torch::Tensor G, torch::Tensor O,
     c10::optional<torch::Tensor> tA, c10::optional<torch::Tensor> tB,
     c10::optional<torch::Tensor> tG, c10::optional<torch::Tensor> tO,
-    torch::Tensor entries, torch::Tensor coefs, long omask, long order) {
+    torch::Tensor entries, torch::Tensor coefs, long omask, long order,
+    long static_id) {
   TORCH_CHECK(A.is_cuda() && A.dim() == 3 && B.dim() == 2 &&
               G.dim() == 3 && O.dim() == 3, "etp_sweep: bad ranks");
   TORCH_CHECK(order == 1 || order == 2, "etp_sweep: order is 1 or 2");
@@ -973,14 +1001,10 @@ std::vector<torch::Tensor> etp_sweep(
     }
   }
   const long NC = rows * nch;
+  bool on_static = false;
+  // packed row accesses need every base on a 16-byte boundary
+  bool vec = etp_sweep_vec();
   if (NC > 0) {
-    const int block = etp_sweep_block_size();
-    const size_t lds_bytes = (size_t)etp_sweep_lds_bytes(
-        da, db, dg, do_, n_ent, tmask, omask, dbl ? 8 : 4);
-    TORCH_CHECK(lds_bytes <= 150 * 1024, "etp_sweep LDS budget exceeded");
-    const long blocks = (NC + block - 1) / block;
-    // packed row accesses need every base on a 16-byte boundary
-    bool vec = etp_sweep_vec();
     auto aligned = [](const torch::Tensor& t) {
       return !t.defined() ||
              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
@@ -989,6 +1013,28 @@ std::vector<torch::Tensor> etp_sweep(
       vec = vec && aligned(*prim[s]) && aligned(outs[s]) &&
             (!tang[s]->has_value() || aligned(**tang[s]));
     }
+    if (static_id >= 0 && direct_b) {
+      // compile-time table (etp_static.hip): registers only, no LDS
+      const void* pp[4];
+      const void* tp[4];
+      void* op[4];
+      for (int s = 0; s < 4; ++s) {
+        pp[s] = prim[s]->data_ptr();
+        tp[s] = tang[s]->has_value() ? (*tang[s])->data_ptr() : nullptr;
+        op[s] = outs[s].defined() ? outs[s].data_ptr() : nullptr;
+      }
+      on_static = etp_static_launch(
+          static_id, (int)order, (int)omask, tmask, A.scalar_type(), rows,
+          nch, da, db, dg, do_, pp, tp, op, vec);
+    }
+  }
+  if (NC > 0 && !on_static) {
+    etp_count_generic();
+    const int block = etp_sweep_block_size();
+    const size_t lds_bytes = (size_t)etp_sweep_lds_bytes(
+        da, db, dg, do_, n_ent, tmask, omask, dbl ? 8 : 4);
+    TORCH_CHECK(lds_bytes <= 150 * 1024, "etp_sweep LDS budget exceeded");
+    const long blocks = (NC + block - 1) / block;
     AT_DISPATCH_FLOATING_TYPES_AND2(
         at::ScalarType::BFloat16, at::ScalarType::Half, A.scalar_type(),
         "etp_sweep", [&] {

@@ -646,7 +646,8 @@ torch::Tensor etp_general(torch::Tensor A, torch::Tensor B, torch::Tensor C,
                           torch::Tensor o_ranges, long do_,
                           c10::optional<torch::Tensor> ai,
                           c10::optional<torch::Tensor> bi,
-                          c10::optional<torch::Tensor> ci, long n_rows);
+                          c10::optional<torch::Tensor> ci, long n_rows,
+                          long static_id);
 torch::Tensor etp_nodesum(torch::Tensor A, torch::Tensor B,
                           torch::Tensor C, torch::Tensor entries,
                           torch::Tensor coefs, long do_,
@@ -664,9 +665,14 @@ std::vector<torch::Tensor> etp_sweep(
     torch::Tensor A, torch::Tensor B, torch::Tensor G, torch::Tensor O,
     c10::optional<torch::Tensor> tA, c10::optional<torch::Tensor> tB,
     c10::optional<torch::Tensor> tG, c10::optional<torch::Tensor> tO,
-    torch::Tensor entries, torch::Tensor coefs, long omask, long order);
+    torch::Tensor entries, torch::Tensor coefs, long omask, long order,
+    long static_id);
 long etp_sweep_lds_bytes(long da, long db, long dg, long do_, long n_ent,
                          long tmask, long omask, long acc_bytes);
+// defined in etp_static.hip
+bool etp_static_supported(long table_id, long order, long omask,
+                          long tmask);
+std::vector<long> etp_path_counts();
 
 // defined in varlen_attn.hip
 torch::Tensor varlen_attention(torch::Tensor Q, torch::Tensor K,
@@ -779,7 +785,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("ai") = pybind11::none(),
         pybind11::arg("bi") = pybind11::none(),
         pybind11::arg("ci") = pybind11::none(),
-        pybind11::arg("n_rows") = 0);
+        pybind11::arg("n_rows") = 0, pybind11::arg("static_id") = -1);
   m.def("etp_nodesum", &etp_nodesum, "fused gather+TP+segment sum (HIP)",
         pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("C"),
         pybind11::arg("entries"), pybind11::arg("coefs"),
@@ -807,9 +813,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("tG") = pybind11::none(),
         pybind11::arg("tO") = pybind11::none(),
         pybind11::arg("entries"), pybind11::arg("coefs"),
-        pybind11::arg("omask"), pybind11::arg("order") = 1);
+        pybind11::arg("omask"), pybind11::arg("order") = 1,
+        pybind11::arg("static_id") = -1);
   m.def("etp_sweep_lds_bytes", &etp_sweep_lds_bytes,
         "dynamic-LDS bytes of one etp_sweep block");
+  m.def("etp_static_supported", &etp_static_supported,
+        "whether (static table id, order, omask, tmask) has a "
+        "compile-time-table ETP kernel");
+  m.def("etp_path_counts", &etp_path_counts,
+        "(static-table, run-time-table) ETP launches so far");
   m.def("gather_fwd", &gather_fwd, "gather rows (HIP)");
   m.def("scatter_sum_fwd", &scatter_sum_fwd, "scatter-add (HIP)");
   m.def("segment_sum_csr", &segment_sum_csr, "CSR segment sum (HIP)",

@@ -12,6 +12,9 @@ run on the fused HIP kernels (csrc/etp.hip); CPU uses a dense-einsum
 path that autograd differentiates directly.  The backward passes run
 as sweeps: one launch yields every wanted first derivative, and one
 more the whole second-order contribution (see "Sweep family" below).
+A table that is exactly one of the compiled-in ones (etp_static.py)
+runs its forward and sweeps on the static-table kernels
+(csrc/etp_static.hip, HYDRAGNN_ETP_STATIC) at 64 channels.
 """
 
 from __future__ import annotations
@@ -41,6 +44,17 @@ class ETPTable:
         self._perm_cache: Dict[str, "ETPTable"] = {}
         self._dev_cache: Dict[Tuple, Tuple] = {}
         self._dense_cache: Dict[Tuple, torch.Tensor] = {}
+        self._static_id = None
+
+    @property
+    def static_id(self) -> int:
+        """Id of the compile-time table (csrc/etp_static_tables.inc)
+        this table equals exactly, -1 if none.  Resolved once, on the
+        CPU copies; a permuted table from perm() resolves its own."""
+        if self._static_id is None:
+            from .etp_static import lookup
+            self._static_id = lookup(self.entries, self.coefs, self.dims)
+        return self._static_id
 
     def perm(self, order: str) -> "ETPTable":
         """order: 4-char permutation of 'abgo' giving the new roles,
@@ -129,6 +143,37 @@ _LDS_BUDGET = 150 * 1024
 sweep_stats = {"sweep1": 0, "sweep2": 0, "compose1": 0, "compose2": 0}
 
 
+_STATIC_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _static_id(table: ETPTable) -> int:
+    """HYDRAGNN_ETP_STATIC (default 1): 0 keeps every launch on the
+    run-time-table kernels."""
+    if os.environ.get("HYDRAGNN_ETP_STATIC", "1") == "0":
+        return -1
+    return table.static_id
+
+
+def _static_applies(table: ETPTable, a, order: int, omask: int,
+                    tmask: int) -> bool:
+    """Whether csrc/etp_static.hip takes this launch: a compile-time
+    table, 64 channels, bf16/fp32, and an instantiated (order, omask,
+    tmask).  The same conditions decide in the extension."""
+    sid = _static_id(table)
+    if sid < 0 or a.shape[1] != 64 or a.dtype not in _STATIC_DTYPES:
+        return False
+    return get_extension(required=True).etp_static_supported(
+        sid, order, omask, tmask)
+
+
+def path_counts() -> Dict[str, int]:
+    """Launches of etp_general / etp_sweep so far on the static-table
+    kernels and on the run-time-table kernels (tests read the deltas
+    to see which path ran)."""
+    s, g = get_extension(required=True).etp_path_counts()
+    return {"static": s, "generic": g}
+
+
 def _sweep_mode() -> int:
     """HYDRAGNN_ETP_SWEEP: 0 = single-output kernels only, 1 = fused
     first-order backward, 2 = fused first- and second-order (default)."""
@@ -209,11 +254,15 @@ def _bits(flags) -> int:
 def _sweep_fits(table: ETPTable, primals, tangents, mask) -> bool:
     """Kernel dtype/device conditions plus the sweep's own LDS
     footprint: block x (input + tangent + output rows) x accumulator
-    size + table, against the family's 150 KiB budget."""
+    size + table, against the family's 150 KiB budget.  A launch the
+    static-table kernel takes uses no LDS and always fits."""
     if not _kernel_ok(table, *primals):
         return False
     tmask = 0 if tangents is None else _bits(
         [t is not None for t in tangents])
+    if _static_applies(table, primals[0], 1 if tangents is None else 2,
+                       _bits(mask), tmask):
+        return True
     acc = 8 if primals[0].dtype == torch.float64 else 4
     da, db, dg, do = table.dims
     ext = get_extension(required=True)
@@ -247,7 +296,7 @@ def etp_sweep(primals, tangents, mask, table: ETPTable):
         None if t is None else t.contiguous() for t in tangents]
     outs = ext.etp_sweep(*[p.contiguous() for p in primals], *tang,
                          ent, coefs, _bits(mask),
-                         1 if tangents is None else 2)
+                         1 if tangents is None else 2, _static_id(table))
     return tuple(outs)
 
 
@@ -302,7 +351,7 @@ class _ETPGeneral(torch.autograd.Function):
         ent, coefs, o_ranges = table.device_tensors(A.device)
         return ext.etp_general(A.contiguous(), B.contiguous(),
                                C.contiguous(), ent, coefs, o_ranges,
-                               table.dims[3])
+                               table.dims[3], static_id=_static_id(table))
 
     @staticmethod
     def backward(ctx, gout):

@@ -11,6 +11,7 @@ ext_modules = [
         name="hydragnn_amd.ops._hip_ops",
         sources=["hydragnn_amd/ops/csrc/hip_ops.hip",
                  "hydragnn_amd/ops/csrc/etp.hip",
+                 "hydragnn_amd/ops/csrc/etp_static.hip",
                  "hydragnn_amd/ops/csrc/mfma_linear.hip",
                  "hydragnn_amd/ops/csrc/varlen_attn.hip",
                  "hydragnn_amd/ops/csrc/gemv.hip",

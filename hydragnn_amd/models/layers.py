@@ -17,7 +17,8 @@ from typing import List, Optional
 import torch
 from torch import nn
 
-from ..ops import degree, gather, scatter, segment_softmax
+from ..ops import degree, gather, pna_aggr, scatter, segment_softmax
+from ..ops.scatter import _rowptr_from_sorted
 
 
 class InvariantConvWrapper(nn.Module):
@@ -187,7 +188,34 @@ class DegreeScalerAggregation(nn.Module):
             "avg_deg_log",
             (((bins + 1).log() * deg).sum() / max(num, 1)).clamp(min=1e-6))
 
+    def _fused(self, msg) -> bool:
+        """Device tensors of the kernel dtypes with known aggregators
+        and scalers take the fused op, unless HYDRAGNN_PNA_FUSED=0."""
+        import os
+        return (msg.is_cuda and msg.dim() == 2
+                and msg.dtype in (torch.float32, torch.float64,
+                                  torch.bfloat16, torch.float16)
+                and os.environ.get("HYDRAGNN_PNA_FUSED", "1") != "0"
+                and len(set(self.aggregators)) == len(self.aggregators)
+                and all(a in pna_aggr.AGGREGATORS
+                        for a in self.aggregators)
+                and 0 < len(self.scalers) <= pna_aggr.MAX_SCALERS
+                and all(s in pna_aggr.SCALERS for s in self.scalers))
+
     def forward(self, msg, index, dim_size):
+        if self._fused(msg):
+            if index.dtype != torch.long:
+                index = index.long()
+            perm = None
+            if not getattr(self, "_edges_sorted", False):
+                perm = torch.argsort(index, stable=True)
+            rowptr = _rowptr_from_sorted(index, dim_size)
+            scale = pna_aggr.pna_scale(rowptr, self.scalers,
+                                       self.avg_deg_lin, self.avg_deg_log,
+                                       msg.dtype)
+            return pna_aggr.pna_aggregate(msg, rowptr, scale,
+                                          self.aggregators, perm=perm)
+        pna_aggr.count_composition()
         outs = [scatter(msg, index, dim_size, a,
                         sorted_index=getattr(self, "_edges_sorted",
                                              False))

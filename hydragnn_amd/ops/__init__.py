@@ -25,6 +25,8 @@ from ._extension import has_extension, get_extension
 from .irreps_linear import irreps_linear
 from .varlen_attn import varlen_attention
 from .segment_linear import segment_outer_sum, segment_matvec
+from .pna_aggr import (pna_aggregate, pna_scale, path_counts,
+                       reset_path_counts)
 from .mfma_linear import MFMALinear
 from .splitk_linear import SplitKLinear
 
@@ -37,4 +39,5 @@ __all__ = [
     "has_extension", "get_extension",
     "irreps_linear", "varlen_attention", "MFMALinear", "SplitKLinear",
     "segment_outer_sum", "segment_matvec",
+    "pna_aggregate", "pna_scale", "path_counts", "reset_path_counts",
 ]

@@ -746,7 +746,44 @@ long segment_linear_lds_bytes(long a, long b, at::ScalarType dtype,
 std::vector<long> segment_linear_tiling(long a, long b,
                                         at::ScalarType dtype);
 
+// defined in pna_aggr.hip
+std::vector<torch::Tensor> pna_fwd(torch::Tensor x, torch::Tensor rowptr,
+                                   c10::optional<torch::Tensor> perm,
+                                   torch::Tensor scale,
+                                   std::vector<long> aggs);
+torch::Tensor pna_bwd(torch::Tensor x, torch::Tensor rowptr,
+                      c10::optional<torch::Tensor> perm,
+                      torch::Tensor scale, std::vector<long> aggs,
+                      torch::Tensor stats, torch::Tensor arg,
+                      torch::Tensor G);
+std::vector<torch::Tensor> pna_bwd2(torch::Tensor x, torch::Tensor rowptr,
+                                    c10::optional<torch::Tensor> perm,
+                                    torch::Tensor scale,
+                                    std::vector<long> aggs,
+                                    torch::Tensor stats, torch::Tensor arg,
+                                    torch::Tensor G, torch::Tensor c,
+                                    bool need_G, bool need_x);
+long pna_grid_blocks(long n_threads);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("pna_fwd", &pna_fwd,
+        "fused PNA aggregation -> (out, stats, arg) (HIP); aggregator "
+        "ids: 0 sum, 1 mean, 2 min, 3 max, 4 std, 5 var",
+        pybind11::arg("x"), pybind11::arg("rowptr"), pybind11::arg("perm"),
+        pybind11::arg("scale"), pybind11::arg("aggs"));
+  m.def("pna_bwd", &pna_bwd, "fused PNA aggregation backward -> dx (HIP)",
+        pybind11::arg("x"), pybind11::arg("rowptr"), pybind11::arg("perm"),
+        pybind11::arg("scale"), pybind11::arg("aggs"),
+        pybind11::arg("stats"), pybind11::arg("arg"), pybind11::arg("G"));
+  m.def("pna_bwd2", &pna_bwd2,
+        "fused PNA aggregation second order -> (hG, gx) (HIP)",
+        pybind11::arg("x"), pybind11::arg("rowptr"), pybind11::arg("perm"),
+        pybind11::arg("scale"), pybind11::arg("aggs"),
+        pybind11::arg("stats"), pybind11::arg("arg"), pybind11::arg("G"),
+        pybind11::arg("c"), pybind11::arg("need_G"),
+        pybind11::arg("need_x"));
+  m.def("pna_grid_blocks", &pna_grid_blocks,
+        "blocks of a PNA launch over n (row, feature) threads");
   m.def("segment_outer_sum", &segment_outer_sum,
         "per-segment outer-product sum -> K[G, H, a, b] in the "
         "accumulator type (HIP); z <= 0 picks the row split",

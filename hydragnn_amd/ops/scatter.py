@@ -162,7 +162,10 @@ class _ScatterMean(torch.autograd.Function):
 
 class _ScatterMax(torch.autograd.Function):
     """max (or min) segment reduce. Backward routes gradient to argmax
-    edges only. Not double-backward-critical (force models use sum)."""
+    edges only, through `scatter_add_`: its double backward leaves the
+    kernels.  PNAEq, the force model that aggregates by min/max, goes
+    through `pna_aggr.pna_aggregate` instead, which is closed under
+    differentiation on the device."""
 
     @staticmethod
     def forward(ctx, src, index, dim_size, is_max: bool):

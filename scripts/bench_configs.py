@@ -1,6 +1,9 @@
 """Secondary benchmark configs (BASELINE.json configs[2..4]): PaiNN
 multi-head QM9-shape, EGNN + GPS global attention, DimeNet fp64 with
-gradient checkpointing on periodic cells.  The driver's contract bench
+gradient checkpointing on periodic cells; and the PNA family: PNAEq as
+an MLIP (energy + forces, double backward) and PNAPlus on QM9-shaped
+molecules, both through DegreeScalerAggregation (HYDRAGNN_PNA_FUSED=0
+times the composition instead).  The driver's contract bench
 (bench.py) stays MACE; this script produces the per-config evidence
 lines.
 
@@ -43,6 +46,13 @@ def qm9_shape_multihead(num_samples, seed=23):
     return ds
 
 
+def _graph_only(d):
+    """Keep the graph target of a `qm9_shape_multihead` sample."""
+    d.y = d.y[:1]
+    d.y_loc = torch.tensor([[0, 1]])
+    return d
+
+
 def oc20_shape(num_samples, seed=29, with_pe=False):
     """OC20-shaped surfaces: ~80 atoms, periodic slab."""
     from hydragnn_amd.preprocess import add_laplacian_pe
@@ -54,7 +64,56 @@ def oc20_shape(num_samples, seed=29, with_pe=False):
     return ds
 
 
+def degree_histogram(dataset):
+    """In-degree histogram of a dataset: the `pna_deg` of the PNA
+    stacks."""
+    hist = torch.zeros(1, dtype=torch.long)
+    for d in dataset:
+        deg = torch.bincount(d.edge_index[1], minlength=d.num_nodes)
+        h = torch.bincount(deg)
+        if h.numel() > hist.numel():
+            h[:hist.numel()] += hist
+            hist = h
+        else:
+            hist[:h.numel()] += h
+    return hist.tolist()
+
+
+def md17_shape(num_samples):
+    from hydragnn_amd.utils.datasets.synthetic import md17_shape_dataset
+    return md17_shape_dataset(num_samples=num_samples, radius=5.0,
+                              max_neighbours=32, seed=37)
+
+
+_NODE_HEAD = {"node": [{"type": "branch-0", "architecture": {
+    "num_headlayers": 2, "dim_headlayers": [64, 64], "type": "mlp"}}]}
+_GRAPH_HEAD = {"graph": [{"type": "branch-0", "architecture": {
+    "num_sharedlayers": 1, "dim_sharedlayers": 64, "num_headlayers": 2,
+    "dim_headlayers": [64, 64]}}]}
+
 CONFIGS = {
+    "pnaeq_mlip": dict(
+        label="PNAEq MLIP energy+forces, MD17-shape, fp32",
+        precision="fp32", local_batch=256, mlip=True,
+        data=md17_shape,
+        model=dict(mpnn_type="PNAEq", input_dim=1, hidden_dim=64,
+                   output_dim=[1], output_type=["node"],
+                   output_heads=_NODE_HEAD, task_weights=[1.0],
+                   num_conv_layers=3, radius=5.0, num_radial=20,
+                   max_neighbours=32, equivariance=True,
+                   activation_function="silu",
+                   enable_interatomic_potential=True, energy_weight=1.0,
+                   energy_peratom_weight=0.0, force_weight=10.0)),
+    "pnaplus_qm9": dict(
+        label="PNAPlus graph head, QM9-shape, bf16",
+        precision="bf16", local_batch=256, mlip=False,
+        data=lambda b: [_graph_only(d) for d in qm9_shape_multihead(b)],
+        model=dict(mpnn_type="PNAPlus", input_dim=1, hidden_dim=64,
+                   output_dim=[1], output_type=["graph"],
+                   output_heads=_GRAPH_HEAD, task_weights=[1.0],
+                   num_conv_layers=3, radius=4.0, num_radial=5,
+                   envelope_exponent=5, max_neighbours=20,
+                   activation_function="relu")),
     "painn_qm9": dict(
         label="PaiNN multi-head (graph+node) QM9-shape",
         precision="bf16", local_batch=256, mlip=False,
@@ -144,10 +203,13 @@ def main():
 
     batch_size = args.batch or cfg["local_batch"]
     prec, param_dtype, _ = resolve_precision(cfg["precision"])
-    model = create_model(use_gpu=False, loss_function_type="mse",
-                         **cfg["model"])
-    model = model.to(device=device, dtype=param_dtype)
     data = cfg["data"](batch_size)
+    model_args = dict(cfg["model"])
+    if model_args["mpnn_type"] in ("PNA", "PNAPlus", "PNAEq"):
+        model_args["pna_deg"] = degree_histogram(data)
+    model = create_model(use_gpu=False, loss_function_type="mse",
+                         **model_args)
+    model = model.to(device=device, dtype=param_dtype)
     batch = Batch.from_data_list(data).to(device)
     for key in list(batch.keys()):
         v = batch[key]
@@ -155,13 +217,19 @@ def main():
             batch[key] = v.to(param_dtype)
     opt = torch.optim.AdamW(model.parameters(), lr=1e-3)
     autocast, _ = get_autocast_and_scaler(cfg["precision"])
-    head_index = get_head_indices(model, batch)
+    head_index = None if cfg["mlip"] else get_head_indices(model, batch)
 
     def step():
         opt.zero_grad(set_to_none=True)
+        if cfg["mlip"]:
+            batch.pos.requires_grad_(True)
         with autocast:
             pred = model(batch)
-            loss, _ = model.loss(pred, batch.y, head_index)
+            if cfg["mlip"]:
+                loss, _ = model.energy_force_loss(pred, batch,
+                                                  create_graph=True)
+            else:
+                loss, _ = model.loss(pred, batch.y, head_index)
         loss.backward()
         opt.step()
         return loss

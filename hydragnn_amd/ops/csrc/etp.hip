@@ -4,23 +4,28 @@
 //   out[i, c, o] = sum_entries coef * A[i, c, a] * B[i, b] * C[i, c, g]
 // (entry table = flattened Wigner-3j paths).  hipBLASLt runs these as
 // tiny-batched GEMMs at ~2% of HBM bandwidth; here one kernel does the
-// whole contraction: a 32-thread group per (i, c) pair stages the A/B/C
-// rows in LDS, each thread owns one output index and walks its slice of
-// the (sorted-by-output) entry table.  VGPR use stays low (no
-// runtime-indexed register arrays -> no scratch), so occupancy is high
-// and the kernel runs at the memory-bound roofline.
+// whole contraction: one thread per (i, c) keeps its A/B/C rows and its
+// output row in a per-thread LDS slice and walks the (sorted-by-output)
+// entry table, staged in LDS once per block.  VGPR use stays low (no
+// runtime-indexed register arrays -> no scratch).
 //
-// The same kernel computes every first- and second-order derivative of
-// the contraction: gradients of a trilinear form are trilinear forms
-// with role-permuted entry tables (see ops/etp.py), so force training
-// (create_graph=True double backward) never leaves this kernel family.
-// The sweep kernels at the end of the file produce several of those
-// derivatives per launch, with every row staged once.
+// The same kernel template (etp_form_kernel) computes every first- and
+// second-order derivative of the contraction: gradients of a trilinear
+// form are trilinear forms with role-permuted entry tables (see
+// ops/etp.py), and the channel-reduced b-slot gradient is its b-type
+// instance, so force training (create_graph=True double backward) never
+// leaves this kernel family.  The sweep kernels at the end of the file
+// produce several of those derivatives per launch, with every row
+// staged once.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+
+#include <type_traits>
+
+#include "check_launch.h"
 
 namespace {
 
@@ -29,431 +34,186 @@ namespace {
 template <typename T> struct acc_of { using type = float; };
 template <> struct acc_of<double> { using type = double; };
 
-// out[i,c,o] = sum over entries(coef, a, b, g, o) of
-//              coef * A[i,c,a] * B[i,b] * C[i,c,g]
+// ---- helpers shared by the single-output form and the sweep ---------
+
+// Dynamic LDS of a block: one slice of `stride` accumulator words per
+// thread, then the entry table (int4 + float per entry) on a 16-byte
+// boundary.  Host (footprint) and device (addresses) both use this.
+__host__ __device__ inline size_t slice_bytes(int block, int stride,
+                                              size_t acc_bytes) {
+  return ((size_t)block * stride * acc_bytes + 15) & ~(size_t)15;
+}
+
+struct StagedTable {
+  const int4* ent;
+  const float* coef;
+};
+
+// Copies the entry table behind the block's slices.  The caller's
+// __syncthreads() publishes it; afterwards every thread walks the same
+// entries in lockstep (wave-uniform LDS broadcasts, no divergence).
+__device__ inline StagedTable stage_table(char* smem, size_t slices,
+                                          const int4* __restrict__ entries,
+                                          const float* __restrict__ coefs,
+                                          int n_ent) {
+  int4* ent_lds = reinterpret_cast<int4*>(smem + slices);
+  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
+  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
+    ent_lds[k] = entries[k];
+    coef_lds[k] = coefs[k];
+  }
+  return {ent_lds, coef_lds};
+}
+
+// Sum of v over the 64 lanes of the wave, valid in lane 0.
+template <typename ACC>
+__device__ inline ACC wave_sum(ACC v) {
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// Channel reduction of a b-type output: out_row[k] += acc[k] over the
+// threads of one row.  With nch % 64 == 0 a wave lies inside one row:
+// shuffle-reduce each k across the 64 lanes, then ONE atomic per k per
+// wave; otherwise one atomic per thread (db <= 12, light contention).
+// Every thread of the block calls this (the shuffles need whole waves).
+template <typename ACC>
+__device__ inline void channel_sum_atomic(ACC* __restrict__ out_row,
+                                          const ACC* acc, int db, int nch,
+                                          bool valid) {
+  if (nch % 64 == 0) {
+    for (int k = 0; k < db; ++k) {
+      ACC v = wave_sum(valid ? acc[k] : (ACC)0);
+      if ((threadIdx.x % 64) == 0 && valid) atomicAdd(&out_row[k], v);
+    }
+  } else if (valid) {
+    for (int k = 0; k < db; ++k) atomicAdd(&out_row[k], acc[k]);
+  }
+}
+
+// Row `e` of a slot tensor, through its optional row-index list.
+__device__ inline long row_of(const long* __restrict__ idx, long e) {
+  return idx ? idx[e] : e;
+}
+
+// ---- single-output form ---------------------------------------------
 //
-// One THREAD per (i, c): its A/B/C rows and do-accumulator live in a
-// per-thread LDS slice (runtime entry indices would force register
-// arrays to scratch otherwise).  Every thread walks the SAME entry
-// list in lockstep (entry words are wave-uniform LDS broadcasts), so
-// there is no divergence; global loads/stores are per-thread
-// contiguous rows -> coalesced across adjacent threads.  Slice stride
-// is padded to an odd word count to spread LDS banks.
-template <typename T>
-__global__ void etp_general_kernel(
-    const T* __restrict__ A, const T* __restrict__ B,
-    const T* __restrict__ C, T* __restrict__ out,
-    const int4* __restrict__ entries,
-    const float* __restrict__ coefs, int n_ent,
-    long NC, int nch, int da, int db, int dg, int do_,
-    const long* __restrict__ ai, const long* __restrict__ bi,
-    const long* __restrict__ ci) {
+// One slot of Q(a,b,g,o) = sum_k coef_k a[a_k] b[b_k] g[g_k] o[o_k] out,
+// the other three in:
+//   o-type (B_OUT = false): out[i,c,o] = sum_k coef A[i,c,a] B[i,b] G[i,c,g]
+//   b-type (B_OUT = true):  out[i,b] = sum_c sum_k coef A[i,c,a] G[i,c,g] O[i,c,o]
+// in0/in1/in2 are the three input slots in slot order.  The same form
+// with role-permuted tables gives every gradient (see ops/etp.py).
+//
+// Per-thread LDS slice, shared by host (footprint) and device: the
+// staged input rows in slot order, then the output slot's accumulator
+// row; odd word stride to spread LDS banks.
+struct FormLayout {
+  int d[3], dout, stride;
+  __host__ __device__ FormLayout(int da, int db, int dg, int do_,
+                                 bool b_out, bool staged) {
+    d[0] = da;
+    d[1] = b_out ? dg : db;
+    d[2] = b_out ? do_ : dg;
+    dout = b_out ? db : do_;
+    stride = ((staged ? d[0] + d[1] + d[2] : 0) + dout) | 1;
+  }
+};
+
+// Entry word of each role: the three inputs in slot order, the output.
+template <bool B_OUT> struct Roles {
+  __device__ static int in0(int4 q) { return q.x; }
+  __device__ static int in1(int4 q) { return B_OUT ? q.z : q.y; }
+  __device__ static int in2(int4 q) { return B_OUT ? q.w : q.z; }
+  __device__ static int out(int4 q) { return B_OUT ? q.y : q.w; }
+};
+
+// One THREAD per (output row, channel): its input rows and accumulator
+// live in a per-thread LDS slice (runtime entry indices would force
+// register arrays to scratch otherwise); global loads/stores are
+// per-thread contiguous rows -> coalesced across adjacent threads.
+//
+// STAGED: input rows are copied into the slice; otherwise only the
+//   accumulator is in LDS and operands are read through L1 per entry
+//   (each row is 1-2 hot cache lines; for shapes whose staged slices
+//   exceed the LDS budget).
+// CSR: the thread sums positions rowptr[r]..rowptr[r+1] of its output
+//   row r, restaging each position's rows (fused gather + tensor
+//   product + segment sum); otherwise position r alone.
+template <typename T, bool B_OUT, bool STAGED, bool CSR>
+__global__ void etp_form_kernel(
+    const T* __restrict__ in0, const T* __restrict__ in1,
+    const T* __restrict__ in2,
+    std::conditional_t<B_OUT, typename acc_of<T>::type, T>* __restrict__ out,
+    const int4* __restrict__ entries, const float* __restrict__ coefs,
+    int n_ent, const long* __restrict__ rowptr, long NC, int nch, int da,
+    int db, int dg, int do_, const long* __restrict__ i0,
+    const long* __restrict__ i1, const long* __restrict__ i2) {
+  static_assert(STAGED || !CSR, "the CSR form restages rows");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using ACC = typename acc_of<T>::type;
-  const int stride = ((da + db + dg + do_) | 1);  // odd word stride
-  ACC* slices = reinterpret_cast<ACC*>(smem);
-  int4* ent_lds = reinterpret_cast<int4*>(
-      smem + (size_t)blockDim.x * stride * sizeof(ACC));
-  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
+  using R = Roles<B_OUT>;
+  const FormLayout L(da, db, dg, do_, B_OUT, STAGED);
+  const StagedTable tab = stage_table(
+      smem, slice_bytes(blockDim.x, L.stride, sizeof(ACC)), entries, coefs,
+      n_ent);
 
-  // stage the entry table once per block
-  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
-    ent_lds[k] = entries[k];
-    coef_lds[k] = coefs[k];
-  }
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < NC;
+  const long r = i / nch;
+  const int c = (int)(i - r * nch);
+  ACC* m0 = reinterpret_cast<ACC*>(smem) + (size_t)threadIdx.x * L.stride;
+  ACC* m1 = m0 + (STAGED ? L.d[0] : 0);
+  ACC* m2 = m1 + (STAGED ? L.d[1] : 0);
+  ACC* mo = m2 + (STAGED ? L.d[2] : 0);
+  const T *p0 = nullptr, *p1 = nullptr, *p2 = nullptr;
 
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  ACC* my = slices + (size_t)threadIdx.x * stride;
-  ACC* ma = my;
-  ACC* mb = ma + da;
-  ACC* mc = mb + db;
-  ACC* mo = mc + dg;
-  if (i < NC) {
-    long e = i / nch;
-    int c = (int)(i - e * nch);
-    long ea = ai ? ai[e] : e;
-    long eb = bi ? bi[e] : e;
-    long ec = ci ? ci[e] : e;
-    const T* ap = A + (ea * nch + c) * da;
-    const T* bp = B + eb * db;
-    const T* cp = C + (ec * nch + c) * dg;
-    for (int k = 0; k < da; ++k) ma[k] = (ACC)ap[k];
-    for (int k = 0; k < db; ++k) mb[k] = (ACC)bp[k];
-    for (int k = 0; k < dg; ++k) mc[k] = (ACC)cp[k];
-    for (int k = 0; k < do_; ++k) mo[k] = 0.f;
-  }
-  __syncthreads();
-  if (i < NC) {
+  // input rows of position e: in1 of the o-type form is the per-row b
+  // slot, every other input is per (row, channel)
+  auto rows_at = [&](long e) {
+    p0 = in0 + (row_of(i0, e) * nch + c) * L.d[0];
+    p1 = in1 + (B_OUT ? row_of(i1, e) * nch + c : row_of(i1, e)) * L.d[1];
+    p2 = in2 + (row_of(i2, e) * nch + c) * L.d[2];
+    if (STAGED) {
+      for (int k = 0; k < L.d[0]; ++k) m0[k] = (ACC)p0[k];
+      for (int k = 0; k < L.d[1]; ++k) m1[k] = (ACC)p1[k];
+      for (int k = 0; k < L.d[2]; ++k) m2[k] = (ACC)p2[k];
+    }
+  };
+  // coef * x * y * z left to right, accumulated in the slice
+  auto walk = [&]() {
     for (int k = 0; k < n_ent; ++k) {
-      int4 q = ent_lds[k];
-      mo[q.w] += coef_lds[k] * ma[q.x] * mb[q.y] * mc[q.z];
+      const int4 q = tab.ent[k];
+      if (STAGED)
+        mo[R::out(q)] +=
+            tab.coef[k] * m0[R::in0(q)] * m1[R::in1(q)] * m2[R::in2(q)];
+      else
+        mo[R::out(q)] += tab.coef[k] * (ACC)p0[R::in0(q)] *
+                         (ACC)p1[R::in1(q)] * (ACC)p2[R::in2(q)];
     }
-    T* op = out + i * do_;
-    for (int k = 0; k < do_; ++k) op[k] = (T)mo[k];
-  }
-}
+  };
 
-// Register-accumulation variant (LDS-pressure fallback): the entry table is
-// sorted by output slot with per-output (start, count) ranges
-// (ETPTable.device_tensors), so each output accumulates in a REGISTER
-// and stores once — the r1 kernel's mo[q.w] += ... formed a serially
-// dependent LDS read-modify-write chain (consecutive entries hit the
-// same address; PMC: SQ busy only ~13% of wall time = latency-bound).
-// The LDS accumulator slice disappears too (smaller stride -> higher
-// occupancy).
-template <typename T>
-__global__ void etp_general_racc_kernel(
-    const T* __restrict__ A, const T* __restrict__ B,
-    const T* __restrict__ C, T* __restrict__ out,
-    const int4* __restrict__ entries,
-    const float* __restrict__ coefs,
-    const int2* __restrict__ o_ranges, int n_ent,
-    long NC, int nch, int da, int db, int dg, int do_,
-    const long* __restrict__ ai, const long* __restrict__ bi,
-    const long* __restrict__ ci) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using ACC = typename acc_of<T>::type;
-  const int stride = ((da + db + dg) | 1);
-  ACC* slices = reinterpret_cast<ACC*>(smem);
-  int4* ent_lds = reinterpret_cast<int4*>(
-      smem + (size_t)blockDim.x * stride * sizeof(ACC));
-  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
-  int2* rng_lds = reinterpret_cast<int2*>(coef_lds + n_ent);
-
-  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
-    ent_lds[k] = entries[k];
-    coef_lds[k] = coefs[k];
-  }
-  for (int k = threadIdx.x; k < do_; k += blockDim.x)
-    rng_lds[k] = o_ranges[k];
-
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  ACC* my = slices + (size_t)threadIdx.x * stride;
-  ACC* ma = my;
-  ACC* mb = ma + da;
-  ACC* mc = mb + db;
-  if (i < NC) {
-    long e = i / nch;
-    int c = (int)(i - e * nch);
-    long ea = ai ? ai[e] : e;
-    long eb = bi ? bi[e] : e;
-    long ec = ci ? ci[e] : e;
-    const T* ap = A + (ea * nch + c) * da;
-    const T* bp = B + eb * db;
-    const T* cp = C + (ec * nch + c) * dg;
-    for (int k = 0; k < da; ++k) ma[k] = (ACC)ap[k];
-    for (int k = 0; k < db; ++k) mb[k] = (ACC)bp[k];
-    for (int k = 0; k < dg; ++k) mc[k] = (ACC)cp[k];
+  if (valid) {
+    if (!CSR) rows_at(r);
+    for (int k = 0; k < L.dout; ++k) mo[k] = 0.f;
   }
   __syncthreads();
-  if (i >= NC) return;
-  T* op = out + i * do_;
-  for (int o = 0; o < do_; ++o) {
-    int s = rng_lds[o].x;
-    int cnt = rng_lds[o].y;
-    ACC acc = (ACC)0;
-    for (int k = s; k < s + cnt; ++k) {
-      int4 q = ent_lds[k];
-      acc += coef_lds[k] * ma[q.x] * mb[q.y] * mc[q.z];
-    }
-    op[o] = (T)acc;
-  }
-}
-
-// Occupancy variant of etp_general: A/B/C rows are PRIVATE per thread
-// and only ~1-3 cache lines each, so after first touch they are
-// L1-hot — staging them in LDS buys nothing but caps the block count
-// at 1/CU (zero latency hiding; PMC showed SQ busy ~10% of kernel
-// wall time).  Here only the runtime-indexed OUTPUT accumulator lives
-// in LDS; operand reads go straight to L1.  The host picks whichever
-// variant yields more blocks/CU.
-template <typename T>
-__global__ void etp_general_l1_kernel(
-    const T* __restrict__ A, const T* __restrict__ B,
-    const T* __restrict__ C, T* __restrict__ out,
-    const int4* __restrict__ entries,
-    const float* __restrict__ coefs, int n_ent,
-    long NC, int nch, int da, int db, int dg, int do_,
-    const long* __restrict__ ai, const long* __restrict__ bi,
-    const long* __restrict__ ci) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using ACC = typename acc_of<T>::type;
-  const int stride = do_ | 1;
-  ACC* slices = reinterpret_cast<ACC*>(smem);
-  int4* ent_lds = reinterpret_cast<int4*>(
-      smem + (size_t)blockDim.x * stride * sizeof(ACC));
-  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
-  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
-    ent_lds[k] = entries[k];
-    coef_lds[k] = coefs[k];
-  }
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  ACC* mo = slices + (size_t)threadIdx.x * stride;
-  __syncthreads();
-  if (i >= NC) return;
-  long e = i / nch;
-  int c = (int)(i - e * nch);
-  long ea = ai ? ai[e] : e;
-  long eb = bi ? bi[e] : e;
-  long ec = ci ? ci[e] : e;
-  const T* ap = A + (ea * nch + c) * da;
-  const T* bp = B + eb * db;
-  const T* cp = C + (ec * nch + c) * dg;
-  for (int k = 0; k < do_; ++k) mo[k] = 0.f;
-  for (int k = 0; k < n_ent; ++k) {
-    int4 q = ent_lds[k];
-    mo[q.w] += coef_lds[k] * (ACC)ap[q.x] * (ACC)bp[q.y] *
-               (ACC)cp[q.z];
-  }
-  T* op = out + i * do_;
-  for (int k = 0; k < do_; ++k) op[k] = (T)mo[k];
-}
-
-// out[e,b] = sum_c sum over entries(coef, a, b, g, o) of
-//            coef * A[e,c,a] * C[e,c,g] * D[e,c,o]
-// (the B-slot gradient: reduce over channels).  Same structure as
-// etp_general: one thread per (e, c), rows + db-accumulator in a
-// per-thread LDS slice, uniform entry walk; the channel reduction is
-// db fp32 atomicAdds per thread (db <= 12, light contention).
-template <typename T>
-__global__ void etp_reduce_kernel(
-    const T* __restrict__ A, const T* __restrict__ C,
-    const T* __restrict__ D,
-    typename acc_of<T>::type* __restrict__ out,
-    const int4* __restrict__ entries,
-    const float* __restrict__ coefs, int n_ent,
-    long E, int nch, int da, int db, int dg, int do_) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using ACC = typename acc_of<T>::type;
-  const int stride = ((da + dg + do_ + db) | 1);
-  ACC* slices = reinterpret_cast<ACC*>(smem);
-  int4* ent_lds = reinterpret_cast<int4*>(
-      smem + (size_t)blockDim.x * stride * sizeof(ACC));
-  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
-  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
-    ent_lds[k] = entries[k];
-    coef_lds[k] = coefs[k];
-  }
-  long NC = E * nch;
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  ACC* my = slices + (size_t)threadIdx.x * stride;
-  ACC* ma = my;
-  ACC* mc = ma + da;
-  ACC* md = mc + dg;
-  ACC* mb = md + do_;
-  if (i < NC) {
-    const T* ap = A + i * da;
-    const T* cp = C + i * dg;
-    const T* dp = D + i * do_;
-    for (int k = 0; k < da; ++k) ma[k] = (ACC)ap[k];
-    for (int k = 0; k < dg; ++k) mc[k] = (ACC)cp[k];
-    for (int k = 0; k < do_; ++k) md[k] = (ACC)dp[k];
-    for (int k = 0; k < db; ++k) mb[k] = 0.f;
-  }
-  __syncthreads();
-  if (i < NC) {
-    for (int k = 0; k < n_ent; ++k) {
-      int4 q = ent_lds[k];
-      mb[q.y] += coef_lds[k] * ma[q.x] * mc[q.z] * md[q.w];
+  if (valid) {
+    if (CSR) {
+      const long lo = rowptr[r], hi = rowptr[r + 1];
+      for (long e = lo; e < hi; ++e) {
+        rows_at(e);
+        walk();
+      }
+    } else {
+      walk();
     }
   }
-  long e = i / nch;
-  if (nch % 64 == 0) {
-    // a wave spans exactly one edge's channels: shuffle-reduce each b
-    // across the 64 lanes, then ONE atomic per b per wave
-    for (int b = 0; b < db; ++b) {
-      ACC v = (i < NC) ? mb[b] : (ACC)0;
-      for (int off = 32; off >= 1; off >>= 1)
-        v += __shfl_down(v, off, 64);
-      if ((threadIdx.x % 64) == 0 && i < NC)
-        atomicAdd(&out[e * db + b], v);
-    }
-  } else if (i < NC) {
-    for (int b = 0; b < db; ++b) atomicAdd(&out[e * db + b], mb[b]);
-  }
-}
-
-// Fused gather + tensor product + segment sum:
-//   out[r, c, o] = sum_{e in rowptr[r]..rowptr[r+1]} sum_k coef_k
-//                  A[ai[e], c, a] B[bi[e], b] C[ci[e], c, g]
-// One thread per (out row, channel); the edge loop restages each
-// edge's rows into the thread's LDS slice — removes the materialized
-// per-edge message tensor, its scatter pass, and the standalone node
-// gather of the unfused pipeline.
-template <typename T>
-__global__ void etp_nodesum_kernel(
-    const T* __restrict__ A, const T* __restrict__ B,
-    const T* __restrict__ C, T* __restrict__ out,
-    const int4* __restrict__ entries,
-    const float* __restrict__ coefs, int n_ent,
-    const long* __restrict__ rowptr, long R, int nch,
-    int da, int db, int dg, int do_,
-    const long* __restrict__ ai, const long* __restrict__ bi,
-    const long* __restrict__ ci) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using ACC = typename acc_of<T>::type;
-  const int stride = ((da + db + dg + do_) | 1);
-  ACC* slices = reinterpret_cast<ACC*>(smem);
-  int4* ent_lds = reinterpret_cast<int4*>(
-      smem + (size_t)blockDim.x * stride * sizeof(ACC));
-  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
-  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
-    ent_lds[k] = entries[k];
-    coef_lds[k] = coefs[k];
-  }
-  long RC = R * nch;
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  ACC* my = slices + (size_t)threadIdx.x * stride;
-  ACC* ma = my;
-  ACC* mb = ma + da;
-  ACC* mc = mb + db;
-  ACC* mo = mc + dg;
-  __syncthreads();
-  if (i >= RC) return;
-  long r = i / nch;
-  int c = (int)(i - r * nch);
-  for (int k = 0; k < do_; ++k) mo[k] = 0.f;
-  long lo = rowptr[r], hi = rowptr[r + 1];
-  for (long e = lo; e < hi; ++e) {
-    long ea = ai ? ai[e] : e;
-    long eb = bi ? bi[e] : e;
-    long ec = ci ? ci[e] : e;
-    const T* ap = A + (ea * nch + c) * da;
-    const T* bp = B + eb * db;
-    const T* cp = C + (ec * nch + c) * dg;
-    for (int k = 0; k < da; ++k) ma[k] = (ACC)ap[k];
-    for (int k = 0; k < db; ++k) mb[k] = (ACC)bp[k];
-    for (int k = 0; k < dg; ++k) mc[k] = (ACC)cp[k];
-    for (int k = 0; k < n_ent; ++k) {
-      int4 q = ent_lds[k];
-      mo[q.w] += coef_lds[k] * ma[q.x] * mb[q.y] * mc[q.z];
-    }
-  }
-  T* op = out + i * do_;
-  for (int k = 0; k < do_; ++k) op[k] = (T)mo[k];
-}
-
-// etp_reduce with per-slot row indices
-template <typename T>
-__global__ void etp_reduce_idx_kernel(
-    const T* __restrict__ A, const T* __restrict__ C,
-    const T* __restrict__ D,
-    typename acc_of<T>::type* __restrict__ out,
-    const int4* __restrict__ entries,
-    const float* __restrict__ coefs, int n_ent,
-    long E, int nch, int da, int db, int dg, int do_,
-    const long* __restrict__ ai, const long* __restrict__ ci,
-    const long* __restrict__ di) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using ACC = typename acc_of<T>::type;
-  const int stride = ((da + dg + do_ + db) | 1);
-  ACC* slices = reinterpret_cast<ACC*>(smem);
-  int4* ent_lds = reinterpret_cast<int4*>(
-      smem + (size_t)blockDim.x * stride * sizeof(ACC));
-  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
-  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
-    ent_lds[k] = entries[k];
-    coef_lds[k] = coefs[k];
-  }
-  long NC = E * nch;
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  ACC* my = slices + (size_t)threadIdx.x * stride;
-  ACC* ma = my;
-  ACC* mc = ma + da;
-  ACC* md = mc + dg;
-  ACC* mb = md + do_;
-  if (i < NC) {
-    long e = i / nch;
-    int c = (int)(i - e * nch);
-    long ea = ai ? ai[e] : e;
-    long ec = ci ? ci[e] : e;
-    long ed = di ? di[e] : e;
-    const T* ap = A + (ea * nch + c) * da;
-    const T* cp = C + (ec * nch + c) * dg;
-    const T* dp = D + (ed * nch + c) * do_;
-    for (int k = 0; k < da; ++k) ma[k] = (ACC)ap[k];
-    for (int k = 0; k < dg; ++k) mc[k] = (ACC)cp[k];
-    for (int k = 0; k < do_; ++k) md[k] = (ACC)dp[k];
-    for (int k = 0; k < db; ++k) mb[k] = 0.f;
-  }
-  __syncthreads();
-  if (i < NC) {
-    for (int k = 0; k < n_ent; ++k) {
-      int4 q = ent_lds[k];
-      mb[q.y] += coef_lds[k] * ma[q.x] * mc[q.z] * md[q.w];
-    }
-  }
-  long e = i / nch;
-  if (nch % 64 == 0) {
-    for (int b = 0; b < db; ++b) {
-      ACC v = (i < NC) ? mb[b] : (ACC)0;
-      for (int off = 32; off >= 1; off >>= 1)
-        v += __shfl_down(v, off, 64);
-      if ((threadIdx.x % 64) == 0 && i < NC)
-        atomicAdd(&out[e * db + b], v);
-    }
-  } else if (i < NC) {
-    for (int b = 0; b < db; ++b) atomicAdd(&out[e * db + b], mb[b]);
-  }
-}
-
-// L1-operand reduce variant: only the small db-accumulator lives in
-// LDS; A/C/D rows are read straight through L1 (each row is 1-2 hot
-// cache lines).  LDS per thread drops from (da+dg+do+db) to db words
-// -> ~6x more waves per CU than the staged variant; the staged reduce
-// measured only ~700-950 GB/s of the 8 TB/s roofline (latency-bound
-// at 1-2 workgroups/CU).
-template <typename T>
-__global__ void etp_reduce_l1_kernel(
-    const T* __restrict__ A, const T* __restrict__ C,
-    const T* __restrict__ D,
-    typename acc_of<T>::type* __restrict__ out,
-    const int4* __restrict__ entries,
-    const float* __restrict__ coefs, int n_ent,
-    long E, int nch, int da, int db, int dg, int do_,
-    const long* __restrict__ ai, const long* __restrict__ ci,
-    const long* __restrict__ di) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using ACC = typename acc_of<T>::type;
-  const int stride = db | 1;
-  ACC* slices = reinterpret_cast<ACC*>(smem);
-  int4* ent_lds = reinterpret_cast<int4*>(
-      smem + (size_t)blockDim.x * stride * sizeof(ACC));
-  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
-  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
-    ent_lds[k] = entries[k];
-    coef_lds[k] = coefs[k];
-  }
-  long NC = E * nch;
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  ACC* mb = slices + (size_t)threadIdx.x * stride;
-  __syncthreads();
-  long e = i / nch;
-  if (i < NC) {
-    int c = (int)(i - e * nch);
-    long ea = ai ? ai[e] : e;
-    long ec = ci ? ci[e] : e;
-    long ed = di ? di[e] : e;
-    const T* ap = A + (ea * nch + c) * da;
-    const T* cp = C + (ec * nch + c) * dg;
-    const T* dp = D + (ed * nch + c) * do_;
-    for (int k = 0; k < db; ++k) mb[k] = 0.f;
-    for (int k = 0; k < n_ent; ++k) {
-      int4 q = ent_lds[k];
-      mb[q.y] += coef_lds[k] * (ACC)ap[q.x] * (ACC)cp[q.z] *
-                 (ACC)dp[q.w];
-    }
-  }
-  if (nch % 64 == 0) {
-    for (int b = 0; b < db; ++b) {
-      ACC v = (i < NC) ? mb[b] : (ACC)0;
-      for (int off = 32; off >= 1; off >>= 1)
-        v += __shfl_down(v, off, 64);
-      if ((threadIdx.x % 64) == 0 && i < NC)
-        atomicAdd(&out[e * db + b], v);
-    }
-  } else if (i < NC) {
-    for (int b = 0; b < db; ++b) atomicAdd(&out[e * db + b], mb[b]);
+  if constexpr (B_OUT) {
+    channel_sum_atomic(out + r * L.dout, mo, L.dout, nch, valid);
+  } else if (valid) {
+    T* op = out + i * L.dout;
+    for (int k = 0; k < L.dout; ++k) op[k] = (T)mo[k];
   }
 }
 
@@ -466,7 +226,7 @@ __global__ void etp_reduce_l1_kernel(
 
 // Per-thread LDS slice layout, shared by host (footprint) and device:
 // four primal rows, then the present tangent rows, then the masked
-// output rows; odd word stride as in etp_general_kernel.
+// output rows; odd word stride as in FormLayout.
 struct SweepLayout {
   int p[4], t[4], o[4], stride;
   __host__ __device__ SweepLayout(int da, int db, int dg, int do_,
@@ -542,7 +302,7 @@ __device__ inline void store_row(T* __restrict__ p, const ACC* src, int d,
 // ORDER 1: out_s = dQ/ds at the primals, for each s in omask.
 // ORDER 2: out_s = sum over r != s with a tangent present of dQ/ds with
 //          slot r replaced by its tangent (absent tangents count as 0).
-// Same mapping as etp_general_kernel: one thread per (row, channel),
+// Same mapping as etp_form_kernel: one thread per (row, channel),
 // uniform entry walk, fp32/fp64 accumulation in the LDS slice.  The b
 // output is per row: with nch == 64 one wave is exactly one row, so a
 // shuffle reduction ends in one store in the output dtype (outB);
@@ -573,15 +333,11 @@ __global__ void etp_sweep_kernel(
   const bool hta = tm & 1, htb = tm & 2, htg = tm & 4, hto = tm & 8;
   const SweepLayout L(da, db, dg, do_, tm, om);
   ACC* slices = reinterpret_cast<ACC*>(smem);
-  // table after the slices, on a 16-byte boundary for the int4 reads
-  size_t slice_bytes =
-      ((size_t)blockDim.x * L.stride * sizeof(ACC) + 15) & ~(size_t)15;
-  int4* ent_lds = reinterpret_cast<int4*>(smem + slice_bytes);
-  float* coef_lds = reinterpret_cast<float*>(ent_lds + n_ent);
-  for (int k = threadIdx.x; k < n_ent; k += blockDim.x) {
-    ent_lds[k] = entries[k];
-    coef_lds[k] = coefs[k];
-  }
+  const StagedTable tab = stage_table(
+      smem, slice_bytes(blockDim.x, L.stride, sizeof(ACC)), entries, coefs,
+      n_ent);
+  const int4* ent_lds = tab.ent;
+  const float* coef_lds = tab.coef;
 
   const long NC = rows * nch;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -669,9 +425,7 @@ __global__ void etp_sweep_kernel(
     if (nch == 64) {
       // blockDim is a multiple of 64, so this wave holds row e whole
       for (int k = 0; k < db; ++k) {
-        ACC v = valid ? rb[k] : (ACC)0;
-        for (int off = 32; off >= 1; off >>= 1)
-          v += __shfl_down(v, off, 64);
+        const ACC v = wave_sum(valid ? rb[k] : (ACC)0);
         if ((threadIdx.x & 63) == 0 && valid) outB[e * db + k] = (T)v;
       }
     } else if (valid) {
@@ -703,47 +457,118 @@ static bool etp_sweep_vec() {
   return v;
 }
 
+// Block size from the environment: 64, 128, 256 or 512, else `dflt`.
+static int env_block(const char* name, int dflt) {
+  const char* e = getenv(name);
+  int v = e ? atoi(e) : dflt;
+  return (v == 64 || v == 128 || v == 256 || v == 512) ? v : dflt;
+}
+
 static int etp_block_size() {
-  static int b = []() {
-    const char* e = getenv("HYDRAGNN_ETP_BLOCK");
-    int v = e ? atoi(e) : 256;
-    return (v == 64 || v == 128 || v == 256 || v == 512) ? v : 256;
-  }();
+  static int b = env_block("HYDRAGNN_ETP_BLOCK", 256);
   return b;
 }
 
-// etp_reduce prefers larger blocks (micro-bench: 512 -> +30% BW over
-// 256 on the b1024 gY shape); separately tunable.
+// the b-type form prefers larger blocks (micro-bench: 512 -> +30% BW
+// over 256 on the b1024 gY shape); separately tunable.
 static int etp_reduce_block_size() {
-  static int b = []() {
-    const char* e = getenv("HYDRAGNN_ETP_REDUCE_BLOCK");
-    int v = e ? atoi(e) : 512;
-    return (v == 64 || v == 128 || v == 256 || v == 512) ? v : 512;
-  }();
+  static int b = env_block("HYDRAGNN_ETP_REDUCE_BLOCK", 512);
   return b;
 }
 
-static const long* idx_ptr(const c10::optional<torch::Tensor>& t) {
-  return t.has_value() ? t->data_ptr<long>() : nullptr;
+static int etp_sweep_block_size() {
+  static int b = env_block("HYDRAGNN_ETP_SWEEP_BLOCK", 128);
+  return b;
+}
+
+constexpr size_t ETP_LDS_BUDGET = 150 * 1024;
+
+// Dynamic-LDS bytes of one block of the single-output form, at the
+// block size its launcher uses: block x slice x accumulator size +
+// staged table.  launch_form() and ops/etp.py both ask this.
+long etp_form_lds_bytes(long da, long db, long dg, long do_, long n_ent,
+                        long acc_bytes, bool b_out, bool staged) {
+  FormLayout L((int)da, (int)db, (int)dg, (int)do_, b_out, staged);
+  int block = b_out ? etp_reduce_block_size() : etp_block_size();
+  return (long)(slice_bytes(block, L.stride, acc_bytes) +
+                (size_t)n_ent * 20);
+}
+
+using OptTensor = c10::optional<torch::Tensor>;
+
+// One launch of the single-output form over `rows` output rows; the
+// argument marshalling every entry point below shares.  in[] and idx[]
+// are the three input slots in slot order and their optional row-index
+// lists; d[] = (da, db, dg, do).  A rowptr selects the CSR instance.
+static void launch_form(const char* what, bool b_out, bool staged,
+                        const torch::Tensor (&in)[3],
+                        const OptTensor (&idx)[3], const OptTensor& rowptr,
+                        torch::Tensor& out, const torch::Tensor& entries,
+                        const torch::Tensor& coefs, long rows, int nch,
+                        const int (&d)[4]) {
+  TORCH_CHECK(b_out ? !rowptr.has_value() : staged, what,
+              ": no such instance");
+  TORCH_CHECK(entries.is_contiguous() && coefs.is_contiguous() &&
+              entries.size(0) == coefs.size(0));
+  const int n_ent = entries.size(0);
+  const at::ScalarType dtype = in[0].scalar_type();
+  const size_t lds_bytes = (size_t)etp_form_lds_bytes(
+      d[0], d[1], d[2], d[3], n_ent,
+      dtype == at::ScalarType::Double ? 8 : 4, b_out, staged);
+  TORCH_CHECK(lds_bytes <= ETP_LDS_BUDGET, what, " LDS budget exceeded");
+  const int block = b_out ? etp_reduce_block_size() : etp_block_size();
+  const long NC = rows * nch;
+  const long blocks = (NC + block - 1) / block;
+  auto ip = [&](int s) -> const long* {
+    return idx[s].has_value() ? idx[s]->data_ptr<long>() : nullptr;
+  };
+  // fp64 runs with double LDS slices (acc_of<double>); others stage fp32
+  AT_DISPATCH_FLOATING_TYPES_AND2(
+      at::ScalarType::BFloat16, at::ScalarType::Half, dtype, "etp_form",
+      [&] {
+        using ACC = typename acc_of<scalar_t>::type;
+        auto launch = [&](auto kern, auto* outp) {
+          hipLaunchKernelGGL(
+              kern, dim3(blocks), dim3(block), lds_bytes, etp_stream(),
+              in[0].data_ptr<scalar_t>(), in[1].data_ptr<scalar_t>(),
+              in[2].data_ptr<scalar_t>(), outp,
+              reinterpret_cast<const int4*>(entries.data_ptr<int>()),
+              coefs.data_ptr<float>(), n_ent,
+              rowptr.has_value() ? rowptr->data_ptr<long>() : nullptr, NC,
+              nch, d[0], d[1], d[2], d[3], ip(0), ip(1), ip(2));
+        };
+        if (b_out && staged)
+          launch(etp_form_kernel<scalar_t, true, true, false>,
+                 out.data_ptr<ACC>());
+        else if (b_out)
+          launch(etp_form_kernel<scalar_t, true, false, false>,
+                 out.data_ptr<ACC>());
+        else if (rowptr.has_value())
+          launch(etp_form_kernel<scalar_t, false, true, true>,
+                 out.data_ptr<scalar_t>());
+        else
+          launch(etp_form_kernel<scalar_t, false, true, false>,
+                 out.data_ptr<scalar_t>());
+      });
+  check_launch(what);
 }
 
 torch::Tensor etp_general(torch::Tensor A, torch::Tensor B, torch::Tensor C,
                           torch::Tensor entries, torch::Tensor coefs,
-                          torch::Tensor o_ranges, long do_,
-                          c10::optional<torch::Tensor> ai,
+                          long do_, c10::optional<torch::Tensor> ai,
                           c10::optional<torch::Tensor> bi,
                           c10::optional<torch::Tensor> ci,
                           long n_rows, long static_id) {
   TORCH_CHECK(A.is_cuda() && A.is_contiguous());
   TORCH_CHECK(B.is_contiguous() && C.is_contiguous());
   long E = n_rows > 0 ? n_rows : A.size(0);
-  long NC = E * A.size(1);
   int nch = A.size(1);
-  int da = A.size(2), db = B.size(1), dg = C.size(2);
-  TORCH_CHECK(da <= 192 && db <= 192 && dg <= 192 && do_ <= 192,
+  const int d[4] = {(int)A.size(2), (int)B.size(1), (int)C.size(2),
+                    (int)do_};
+  TORCH_CHECK(d[0] <= 192 && d[1] <= 192 && d[2] <= 192 && d[3] <= 192,
               "etp dims exceed kernel limits");
   auto out = torch::empty({E, A.size(1), do_}, A.options());
-  if (NC == 0) return out;
+  if (E * nch == 0) return out;
   if (static_id >= 0 && !ai.has_value() && !bi.has_value() &&
       !ci.has_value() && E == A.size(0) && B.size(0) == E &&
       C.size(0) == E && C.size(1) == nch &&
@@ -759,76 +584,20 @@ torch::Tensor etp_general(torch::Tensor A, torch::Tensor B, torch::Tensor C,
                           (const void*)outp[3]})
       vec = vec && reinterpret_cast<uintptr_t>(p) % 16 == 0;
     if (etp_static_launch(static_id, 0, 8, 0, A.scalar_type(), E, nch,
-                          da, db, dg, (int)do_, prim, tang, outp, vec))
+                          d[0], d[1], d[2], d[3], prim, tang, outp, vec))
       return out;
   }
   etp_count_generic();
-  int n_ent = entries.size(0);
-  int block = etp_block_size();
-  size_t accs = A.scalar_type() == at::ScalarType::Double ? 8 : 4;
-  int stride = (da + db + dg + (int)do_) | 1;
-  size_t lds_full = (size_t)block * stride * accs + n_ent * 20;
-  int stride_l1 = (int)do_ | 1;
-  size_t lds_l1 = (size_t)block * stride_l1 * accs + n_ent * 20;
-  // Variant choice (A/B'd on the default bench):
-  //  - racc (r2 default): register accumulation over the
-  //    output-sorted entry ranges — no LDS RMW dependency chain, no
-  //    output slice in LDS.
-  //  - staged (r1): full A/B/C/out slices in LDS.
-  //  - L1: operands from L1, only the accumulator in LDS.
-  // Fallback order by LDS budget; HYDRAGNN_ETP_VARIANT=staged|l1|racc
-  // overrides.
-  int stride_racc = (da + db + dg) | 1;
-  size_t lds_racc = (size_t)block * stride_racc * accs + n_ent * 20 +
-                    (size_t)do_ * 8;
-  // Measured A/B (b1024 bench, same box): staged 30.8k g/s end-to-end
-  // vs racc 29.8k — staged stays the default; racc (smaller slices)
-  // is the fallback when the staged LDS budget is exceeded.
-  int variant = lds_full <= 150 * 1024 ? 0
-                : (lds_racc <= 150 * 1024 ? 2 : 1);
-  const char* env = getenv("HYDRAGNN_ETP_VARIANT");
-  if (env) {
-    if (env[0] == 's') variant = 0;
-    else if (env[0] == 'l') variant = 1;
-    else if (env[0] == 'r') variant = 2;
-  }
-  size_t lds_bytes = variant == 2 ? lds_racc
-                     : (variant == 1 ? lds_l1 : lds_full);
-  TORCH_CHECK(lds_bytes <= 150 * 1024, "etp LDS budget exceeded");
-  long blocks = (NC + block - 1) / block;
-  auto orng = o_ranges.to(torch::kInt32).contiguous();
-  // fp64 runs with double LDS slices (acc_of<double>); others stage fp32
-  AT_DISPATCH_FLOATING_TYPES_AND2(
-      at::ScalarType::BFloat16, at::ScalarType::Half, A.scalar_type(),
-      "etp_general", [&] {
-        if (variant == 2) {
-          hipLaunchKernelGGL(
-              etp_general_racc_kernel<scalar_t>, dim3(blocks),
-              dim3(block), lds_bytes, etp_stream(),
-              A.data_ptr<scalar_t>(), B.data_ptr<scalar_t>(),
-              C.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(),
-              reinterpret_cast<const int4*>(entries.data_ptr<int>()),
-              coefs.data_ptr<float>(),
-              reinterpret_cast<const int2*>(orng.data_ptr<int>()),
-              n_ent, NC, nch, da, db, dg, (int)do_,
-              idx_ptr(ai), idx_ptr(bi), idx_ptr(ci));
-          return;
-        }
-        auto kern = variant == 1 ? etp_general_l1_kernel<scalar_t>
-                                 : etp_general_kernel<scalar_t>;
-        hipLaunchKernelGGL(
-            kern, dim3(blocks), dim3(block),
-            lds_bytes, etp_stream(),
-            A.data_ptr<scalar_t>(), B.data_ptr<scalar_t>(),
-            C.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(),
-            reinterpret_cast<const int4*>(entries.data_ptr<int>()),
-            coefs.data_ptr<float>(), n_ent,
-            NC, nch, da, db, dg, (int)do_,
-            idx_ptr(ai), idx_ptr(bi), idx_ptr(ci));
-      });
+  launch_form("etp_general", false, true, {A, B, C}, {ai, bi, ci},
+              c10::nullopt, out, entries, coefs, E, nch, d);
   return out;
 }
 
+// Fused gather + tensor product + segment sum:
+//   out[r, c, o] = sum_{e in rowptr[r]..rowptr[r+1]} sum_k coef_k
+//                  A[ai[e], c, a] B[bi[e], b] C[ci[e], c, g]
+// removes the materialized per-edge message tensor, its scatter pass,
+// and the standalone node gather of the unfused pipeline.
 torch::Tensor etp_nodesum(torch::Tensor A, torch::Tensor B,
                           torch::Tensor C, torch::Tensor entries,
                           torch::Tensor coefs, long do_,
@@ -840,33 +609,18 @@ torch::Tensor etp_nodesum(torch::Tensor A, torch::Tensor B,
   TORCH_CHECK(B.is_contiguous() && C.is_contiguous());
   long R = rowptr.numel() - 1;
   int nch = A.size(1);
-  int da = A.size(2), db = B.size(1), dg = C.size(2);
+  const int d[4] = {(int)A.size(2), (int)B.size(1), (int)C.size(2),
+                    (int)do_};
   auto out = torch::empty({R, (long)nch, do_}, A.options());
-  long RC = R * nch;
-  if (RC == 0) return out;
-  int n_ent = entries.size(0);
-  int block = etp_block_size();
-  int stride = (da + db + dg + (int)do_) | 1;
-  size_t accs = A.scalar_type() == at::ScalarType::Double ? 8 : 4;
-  size_t lds_bytes = (size_t)block * stride * accs + n_ent * 20;
-  TORCH_CHECK(lds_bytes <= 150 * 1024, "etp LDS budget exceeded");
-  long blocks = (RC + block - 1) / block;
-  AT_DISPATCH_FLOATING_TYPES_AND2(
-      at::ScalarType::BFloat16, at::ScalarType::Half, A.scalar_type(),
-      "etp_nodesum", [&] {
-        hipLaunchKernelGGL(
-            etp_nodesum_kernel<scalar_t>, dim3(blocks), dim3(block),
-            lds_bytes, etp_stream(),
-            A.data_ptr<scalar_t>(), B.data_ptr<scalar_t>(),
-            C.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(),
-            reinterpret_cast<const int4*>(entries.data_ptr<int>()),
-            coefs.data_ptr<float>(), n_ent,
-            rowptr.data_ptr<long>(), R, nch, da, db, dg, (int)do_,
-            idx_ptr(ai), idx_ptr(bi), idx_ptr(ci));
-      });
+  if (R * nch == 0) return out;
+  launch_form("etp_nodesum", false, true, {A, B, C}, {ai, bi, ci}, rowptr,
+              out, entries, coefs, R, nch, d);
   return out;
 }
 
+// out[e,b] = sum_c sum_k coef A[ai[e],c,a] C[ci[e],c,g] D[di[e],c,o]
+// (the B-slot gradient).  The kernel adds into a zeroed accumulator
+// buffer; one cast to the input dtype follows.
 torch::Tensor etp_reduce(torch::Tensor A, torch::Tensor C, torch::Tensor D,
                          torch::Tensor entries, torch::Tensor coefs,
                          long db,
@@ -875,59 +629,32 @@ torch::Tensor etp_reduce(torch::Tensor A, torch::Tensor C, torch::Tensor D,
                          c10::optional<torch::Tensor> di,
                          long n_rows) {
   TORCH_CHECK(A.is_cuda() && A.is_contiguous());
+  TORCH_CHECK(C.is_contiguous() && D.is_contiguous());
   long E = n_rows > 0 ? n_rows : A.size(0);
   int nch = A.size(1);
-  int da = A.size(2), dg = C.size(2), do_ = D.size(2);
+  const int d[4] = {(int)A.size(2), (int)db, (int)C.size(2),
+                    (int)D.size(2)};
   TORCH_CHECK(db <= 12, "etp_reduce db limit");
+  const bool dbl = A.scalar_type() == at::ScalarType::Double;
   auto out = torch::zeros(
-      {E, db}, A.options().dtype(
-          A.scalar_type() == at::ScalarType::Double ? torch::kDouble
-                                                    : torch::kFloat));
-  if (E == 0) return out.to(A.scalar_type());
-  int n_ent = entries.size(0);
-  int block = etp_reduce_block_size();
-  int stride = (da + dg + do_ + (int)db) | 1;
-  size_t accs = A.scalar_type() == at::ScalarType::Double ? 8 : 4;
-  size_t lds_bytes = (size_t)block * stride * accs + n_ent * 20;
+      {E, db}, A.options().dtype(dbl ? torch::kDouble : torch::kFloat));
+  if (E * nch == 0) return out.to(A.scalar_type());
   // staged is the measured default (963 GB/s vs the L1-operand
-  // variant's 381: repeated per-entry L1 hits lose to LDS reads);
-  // HYDRAGNN_ETP_REDUCE_VARIANT=l1 selects the low-LDS variant for
-  // over-budget shapes
+  // instance's 381: repeated per-entry L1 hits lose to LDS reads); the
+  // L1 instance takes shapes whose staged slices exceed the budget, and
+  // every shape under HYDRAGNN_ETP_REDUCE_VARIANT=l1
   const char* rv = getenv("HYDRAGNN_ETP_REDUCE_VARIANT");
-  size_t lds_l1 = (size_t)block * ((db | 1)) * accs + n_ent * 20;
-  bool use_l1 = (rv && rv[0] == 'l') ||
-                (lds_bytes > 150 * 1024 && lds_l1 <= 150 * 1024);
-  if (use_l1)
-    lds_bytes = (size_t)block * ((db | 1)) * accs + n_ent * 20;
-  TORCH_CHECK(lds_bytes <= 150 * 1024, "etp_reduce LDS budget exceeded");
-  long blocks = (E * nch + block - 1) / block;
-  AT_DISPATCH_FLOATING_TYPES_AND2(
-      at::ScalarType::BFloat16, at::ScalarType::Half, A.scalar_type(),
-      "etp_reduce", [&] {
-        auto kern = use_l1 ? etp_reduce_l1_kernel<scalar_t>
-                           : etp_reduce_idx_kernel<scalar_t>;
-        hipLaunchKernelGGL(
-            kern, dim3(blocks), dim3(block),
-            lds_bytes, etp_stream(), A.data_ptr<scalar_t>(),
-            C.data_ptr<scalar_t>(),
-            D.data_ptr<scalar_t>(), out.data_ptr<typename acc_of<scalar_t>::type>(),
-            reinterpret_cast<const int4*>(entries.data_ptr<int>()),
-            coefs.data_ptr<float>(), n_ent, E, nch, da, (int)db, dg, do_,
-            idx_ptr(ai), idx_ptr(ci), idx_ptr(di));
-      });
+  const long n_ent = entries.size(0);
+  const bool staged =
+      !(rv && rv[0] == 'l') &&
+      (size_t)etp_form_lds_bytes(d[0], d[1], d[2], d[3], n_ent,
+                                 dbl ? 8 : 4, true, true) <= ETP_LDS_BUDGET;
+  launch_form("etp_reduce", true, staged, {A, C, D}, {ai, ci, di},
+              c10::nullopt, out, entries, coefs, E, nch, d);
   return out.to(A.scalar_type());
 }
 
 // ---- sweep family host side ----------------------------------------
-
-static int etp_sweep_block_size() {
-  static int b = []() {
-    const char* e = getenv("HYDRAGNN_ETP_SWEEP_BLOCK");
-    int v = e ? atoi(e) : 128;
-    return (v == 64 || v == 128 || v == 256 || v == 512) ? v : 128;
-  }();
-  return b;
-}
 
 // Dynamic-LDS bytes of one sweep block: block x (input rows + tangent
 // rows + output rows) x accumulator size + staged table.  ops/etp.py
@@ -936,10 +663,8 @@ long etp_sweep_lds_bytes(long da, long db, long dg, long do_, long n_ent,
                          long tmask, long omask, long acc_bytes) {
   SweepLayout L((int)da, (int)db, (int)dg, (int)do_, (int)tmask,
                 (int)omask);
-  size_t slices =
-      ((size_t)etp_sweep_block_size() * L.stride * acc_bytes + 15) &
-      ~(size_t)15;
-  return (long)(slices + (size_t)n_ent * 20);
+  return (long)(slice_bytes(etp_sweep_block_size(), L.stride, acc_bytes) +
+                (size_t)n_ent * 20);
 }
 
 // Returns {out_a, out_b, out_g, out_o}; slots outside omask come back
@@ -1033,7 +758,8 @@ std::vector<torch::Tensor> etp_sweep(
     const int block = etp_sweep_block_size();
     const size_t lds_bytes = (size_t)etp_sweep_lds_bytes(
         da, db, dg, do_, n_ent, tmask, omask, dbl ? 8 : 4);
-    TORCH_CHECK(lds_bytes <= 150 * 1024, "etp_sweep LDS budget exceeded");
+    TORCH_CHECK(lds_bytes <= ETP_LDS_BUDGET,
+                "etp_sweep LDS budget exceeded");
     const long blocks = (NC + block - 1) / block;
     AT_DISPATCH_FLOATING_TYPES_AND2(
         at::ScalarType::BFloat16, at::ScalarType::Half, A.scalar_type(),
@@ -1073,6 +799,7 @@ std::vector<torch::Tensor> etp_sweep(
               coefs.data_ptr<float>(), n_ent, rows, nch, da, db, dg,
               do_, (int)omask, vec);
         });
+    check_launch("etp_sweep");
   }
   if (b_acc.defined()) outs[1] = b_acc.to(A.scalar_type());
   return outs;

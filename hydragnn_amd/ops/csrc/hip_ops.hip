@@ -643,7 +643,7 @@ torch::Tensor mfma_linear(torch::Tensor A, torch::Tensor B,
 // defined in etp.hip
 torch::Tensor etp_general(torch::Tensor A, torch::Tensor B, torch::Tensor C,
                           torch::Tensor entries, torch::Tensor coefs,
-                          torch::Tensor o_ranges, long do_,
+                          long do_,
                           c10::optional<torch::Tensor> ai,
                           c10::optional<torch::Tensor> bi,
                           c10::optional<torch::Tensor> ci, long n_rows,
@@ -669,6 +669,8 @@ std::vector<torch::Tensor> etp_sweep(
     long static_id);
 long etp_sweep_lds_bytes(long da, long db, long dg, long do_, long n_ent,
                          long tmask, long omask, long acc_bytes);
+long etp_form_lds_bytes(long da, long db, long dg, long do_, long n_ent,
+                        long acc_bytes, bool b_out, bool staged);
 // defined in etp_static.hip
 bool etp_static_supported(long table_id, long order, long omask,
                           long tmask);
@@ -818,7 +820,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("etp_general", &etp_general, "fused ETP contraction (HIP)",
         pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("C"),
         pybind11::arg("entries"), pybind11::arg("coefs"),
-        pybind11::arg("o_ranges"), pybind11::arg("do_"),
+        pybind11::arg("do_"),
         pybind11::arg("ai") = pybind11::none(),
         pybind11::arg("bi") = pybind11::none(),
         pybind11::arg("ci") = pybind11::none(),
@@ -854,6 +856,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("static_id") = -1);
   m.def("etp_sweep_lds_bytes", &etp_sweep_lds_bytes,
         "dynamic-LDS bytes of one etp_sweep block");
+  m.def("etp_form_lds_bytes", &etp_form_lds_bytes,
+        "dynamic-LDS bytes of one block of the single-output ETP form "
+        "(o-type or b-type output, rows staged or read through L1)",
+        pybind11::arg("da"), pybind11::arg("db"), pybind11::arg("dg"),
+        pybind11::arg("do_"), pybind11::arg("n_ent"),
+        pybind11::arg("acc_bytes"), pybind11::arg("b_out"),
+        pybind11::arg("staged"));
   m.def("etp_static_supported", &etp_static_supported,
         "whether (static table id, order, omask, tmask) has a "
         "compile-time-table ETP kernel");

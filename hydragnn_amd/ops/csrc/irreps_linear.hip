@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "check_launch.h"
+
 namespace {
 
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
@@ -35,14 +37,6 @@ constexpr int PAD = 8;       // bf16 elems of row padding (16 B)
 // static lmap_s table
 constexpr size_t LDS_BUDGET = 160 * 1024;
 constexpr size_t LDS_STATIC = MAXD * sizeof(int);
-
-// A refused launch (e.g. LDS over the limit) must not hand back the
-// uninitialised output.
-inline void check_launch(const char* what) {
-  hipError_t err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, what, " launch failed: ",
-              hipGetErrorString(err));
-}
 
 template <bool TRANS_W>
 __global__ __launch_bounds__(256) void irreps_linear_kernel(

@@ -45,6 +45,8 @@
 
 #include <algorithm>
 
+#include "check_launch.h"
+
 namespace {
 
 template <typename T> struct sl_acc { using type = float; };
@@ -57,12 +59,6 @@ constexpr int SL_BW = SL_BLOCK / SL_LPR;   // matvec: rows per pass
 constexpr int SL_MAX_A = 128, SL_MAX_B = 132;
 constexpr int SL_MAX_Z = 32;
 constexpr long SL_LDS_BUDGET = 160 * 1024;
-
-inline void check_launch(const char* what) {
-  hipError_t err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, what, " launch failed: ",
-              hipGetErrorString(err));
-}
 
 // Row range of graph g, empty when the pointer is not a valid range of
 // [0, N].

@@ -35,6 +35,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "check_launch.h"
+
 namespace {
 
 template <typename T> struct sc_acc { using type = float; };
@@ -56,12 +58,6 @@ __device__ __forceinline__ Ent unpack(int w) {
   e.j = (w >> 14) & 15;
   e.l = (w >> 18) & 15;
   return e;
-}
-
-inline void check_launch(const char* what) {
-  hipError_t err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, what, " launch failed: ",
-              hipGetErrorString(err));
 }
 
 // Forward: flat thread per (n, c).  Entries arrive sorted by o, so an

@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "check_launch.h"
+
 namespace {
 
 constexpr int kMaxDh = 64;
@@ -690,14 +692,6 @@ __global__ __launch_bounds__(kBlock) void varlen_attn_bwd2_k_kernel(
       store_row<C, T>(gK + koff, gk, sub, dh, scale);
     }
   }
-}
-
-// A refused launch (e.g. LDS over the limit) must not hand back
-// uninitialised outputs.
-inline void check_launch(const char* what) {
-  hipError_t err = hipGetLastError();
-  TORCH_CHECK(err == hipSuccess, what, " launch failed: ",
-              hipGetErrorString(err));
 }
 
 // Calls f(VCfg instance) for the narrowest instance that holds dh.

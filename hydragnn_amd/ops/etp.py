@@ -70,21 +70,16 @@ class ETPTable:
         return t
 
     def device_tensors(self, device):
+        """(entries int32 [n, 4], coefs fp32 [n]) on `device`, stably
+        sorted by output slot: this is the kernels' summation order."""
         key = (device,)
         if key in self._dev_cache:
             return self._dev_cache[key]
-        o = self.entries[:, 3]
-        order = torch.argsort(o, stable=True)
+        order = torch.argsort(self.entries[:, 3], stable=True)
         ent = self.entries[order].to(torch.int32)
         coefs = self.coefs[order]
-        do = self.dims[3]
-        counts = torch.bincount(o[order], minlength=do)
-        starts = torch.zeros(do, dtype=torch.long)
-        starts[1:] = counts.cumsum(0)[:-1]
-        o_ranges = torch.stack([starts, counts], dim=1).to(torch.int32)
         out = (ent.to(device).contiguous(),
-               coefs.to(device).contiguous(),
-               o_ranges.to(device).contiguous())
+               coefs.to(device).contiguous())
         self._dev_cache[key] = out
         return out
 
@@ -106,24 +101,43 @@ def _dense_general(A, B, C, table: ETPTable):
     return torch.einsum("eca,eb,ecg,abgo->eco", A, B, C, W)
 
 
+_LDS_BUDGET = 150 * 1024
+
+
+def _on_kernels(t: torch.Tensor) -> bool:
+    """Device, dtype and mode conditions of the whole family; CPU
+    tensors never reach the extension."""
+    return t.is_cuda and t.dtype in _KERNEL_DTYPES and not use_eager()
+
+
+def _form_fits(table: ETPTable, t, b_out: bool, staged: bool) -> bool:
+    """The single-output form's LDS footprint (csrc/etp.hip,
+    etp_form_lds_bytes: the launcher's own block size; fp64 slices are
+    8 bytes) against the family's budget."""
+    ext = get_extension(required=True)
+    return ext.etp_form_lds_bytes(
+        *table.dims, table.entries.shape[0],
+        8 if t.dtype == torch.float64 else 4, b_out, staged) <= _LDS_BUDGET
+
+
 def _kernel_ok(table: ETPTable, *tensors) -> bool:
-    da, db, dg, do = table.dims
-    # real constraint is the per-block LDS budget (256 thread slices +
-    # staged entry table) — mirrors the check in csrc/etp.hip.  Kept
-    # at the FULL-staging footprint even though etp_general can fall
-    # to its L1-operand variant: the gradient kernels (etp_reduce)
-    # still stage fully, and this predicate gates the whole family.
-    # fp64 slices are 8 bytes (full-precision accumulation in LDS).
+    """Whether the o-type form takes this launch; the dense path takes
+    it otherwise.  This predicate gates the whole family (folds,
+    sweeps): over the staged footprint nothing of it runs."""
     t = tensors[0]
-    acc = 8 if t.dtype == torch.float64 else 4
-    lds_bytes = 256 * (da + db + dg + do + 1) * acc + \
-        table.entries.shape[0] * 20
-    if lds_bytes > 150 * 1024 or max(da, db, dg, do) > 192:
-        return False
-    return (t.is_cuda and t.dtype in _KERNEL_DTYPES
+    return (_on_kernels(t)
             and all(x.dtype == t.dtype for x in tensors
                     if torch.is_tensor(x))
-            and not use_eager())
+            and max(table.dims) <= 192
+            and _form_fits(table, t, b_out=False, staged=True))
+
+
+def _reduce_ok(table: ETPTable, t) -> bool:
+    """Whether the b-type form takes this launch: staged within the
+    budget, else (chosen in the extension) on the instance that reads
+    its operands through L1 and keeps only the accumulator in LDS."""
+    return (_on_kernels(t) and table.dims[1] <= 12
+            and _form_fits(table, t, b_out=True, staged=False))
 
 
 # ---------------------------------------------------------------------------
@@ -137,7 +151,6 @@ def _kernel_ok(table: ETPTable, *tensors) -> bool:
 # ---------------------------------------------------------------------------
 _SLOTS = "abgo"
 _SLOT_SUB = {"a": "eca", "b": "eb", "g": "ecg", "o": "eco"}
-_LDS_BUDGET = 150 * 1024
 
 # how often each path ran (tests read this to see a fallback happen)
 sweep_stats = {"sweep1": 0, "sweep2": 0, "compose1": 0, "compose2": 0}
@@ -291,7 +304,7 @@ def etp_sweep(primals, tangents, mask, table: ETPTable):
     if not _sweep_fits(table, primals, tangents, mask):
         return _dense_sweep(primals, tangents, mask, table)
     ext = get_extension(required=True)
-    ent, coefs, _ = table.device_tensors(primals[0].device)
+    ent, coefs = table.device_tensors(primals[0].device)
     tang = [None] * 4 if tangents is None else [
         None if t is None else t.contiguous() for t in tangents]
     outs = ext.etp_sweep(*[p.contiguous() for p in primals], *tang,
@@ -348,9 +361,9 @@ class _ETPGeneral(torch.autograd.Function):
         ctx.save_for_backward(A, B, C)
         ctx.table = table
         ext = get_extension(required=True)
-        ent, coefs, o_ranges = table.device_tensors(A.device)
+        ent, coefs = table.device_tensors(A.device)
         return ext.etp_general(A.contiguous(), B.contiguous(),
-                               C.contiguous(), ent, coefs, o_ranges,
+                               C.contiguous(), ent, coefs,
                                table.dims[3], static_id=_static_id(table))
 
     @staticmethod
@@ -380,7 +393,7 @@ class _ETPReduce(torch.autograd.Function):
         ctx.save_for_backward(A, C, D)
         ctx.table = table
         ext = get_extension(required=True)
-        ent, coefs, _ = table.device_tensors(A.device)
+        ent, coefs = table.device_tensors(A.device)
         return ext.etp_reduce(A.contiguous(), C.contiguous(),
                               D.contiguous(), ent, coefs, table.dims[1])
 
@@ -445,8 +458,7 @@ def fold_last(t: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
 def etp_reduce(A: torch.Tensor, C: torch.Tensor, D: torch.Tensor,
                table: ETPTable) -> torch.Tensor:
     """out[e,b] = sum_c sum_k coef_k A[e,c,a] C[e,c,g] D[e,c,o]."""
-    if (table.dims[1] <= 12 and A.is_cuda
-            and A.dtype in _KERNEL_DTYPES and not use_eager()):
+    if _reduce_ok(table, A):
         return _ETPReduce.apply(A, C, D, table)
     W = table.dense(A.device, torch.float32).to(A.dtype)
     return torch.einsum("eca,ecg,eco,abgo->eb", A, C, D, W)
@@ -543,14 +555,14 @@ class _ETPIndexed(torch.autograd.Function):
         ctx.table = table
         ctx.meta = meta
         ext = get_extension(required=True)
-        ent, coefs, o_ranges = table.device_tensors(A.device)
+        ent, coefs = table.device_tensors(A.device)
         if meta.rowptr is not None:
             return ext.etp_nodesum(A.contiguous(), B.contiguous(),
                                    C.contiguous(), ent, coefs,
                                    table.dims[3], meta.rowptr,
                                    meta.ai, meta.bi, meta.ci)
         return ext.etp_general(A.contiguous(), B.contiguous(),
-                               C.contiguous(), ent, coefs, o_ranges,
+                               C.contiguous(), ent, coefs,
                                table.dims[3], meta.ai, meta.bi,
                                meta.ci, meta.n_positions)
 
@@ -599,7 +611,7 @@ class _ETPReduceIdx(torch.autograd.Function):
         ctx.idx = (ai, ci, di)
         ctx.E = E
         ext = get_extension(required=True)
-        ent, coefs, _ = table.device_tensors(A.device)
+        ent, coefs = table.device_tensors(A.device)
         return ext.etp_reduce(A.contiguous(), C.contiguous(),
                               D.contiguous(), ent, coefs,
                               table.dims[1], ai, ci, di, E)
@@ -646,8 +658,7 @@ class _ETPReduceIdx(torch.autograd.Function):
 def _etp_reduce_idx(A, C, D, table, meta):
     r = meta.r_of_pos()
     di = r if r is not None else None
-    if (A.is_cuda and A.dtype in _KERNEL_DTYPES and not use_eager()
-            and table.dims[1] <= 12):
+    if _reduce_ok(table, A):
         return _ETPReduceIdx.apply(A, C, D, table, meta.ai, meta.ci,
                                    di, meta.n_positions)
     E = meta.n_positions

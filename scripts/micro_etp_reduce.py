@@ -1,9 +1,15 @@
-"""Micro-bench etp_reduce (the B-slot channel-reduce gradient):
-achieved bandwidth vs the HBM roofline, across block sizes."""
+"""Micro-bench the default single-output ETP instances (general,
+channel reduce, CSR form) on the run-time-table kernels at the headline
+shape: median time per call and achieved bandwidth vs the HBM roofline.
 
+    python scripts/micro_etp_reduce.py [reduce_block]
+
+`reduce_block` sets HYDRAGNN_ETP_REDUCE_BLOCK, the block size of the
+channel reduce (64, 128, 256 or 512)."""
+
+import json
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(
     os.path.abspath(__file__))))
@@ -11,8 +17,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(
 import torch  # noqa: E402
 
 
-def run(block):
-    os.environ["HYDRAGNN_ETP_BLOCK"] = str(block)
+def median_us(call, warmup=10, iters=50):
+    for _ in range(warmup):
+        call()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(iters):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        call()
+        t1.record()
+        t1.synchronize()
+        times.append(t0.elapsed_time(t1) * 1e3)
+    return sorted(times)[len(times) // 2]
+
+
+def run(reduce_block=None):
+    if reduce_block is not None:
+        os.environ["HYDRAGNN_ETP_REDUCE_BLOCK"] = str(reduce_block)
     from hydragnn_amd.models.mace.blocks import EdgeTensorProduct
     from hydragnn_amd.ops import etp as etp_mod
 
@@ -20,31 +43,46 @@ def run(block):
     table = tp.etp_table
     da, db, dg, do = table.dims
     E, C = 332358, 64
+    N = E // 26  # nodes of the CSR form, about 26 edges each
     dev = "cuda:0"
-    A = torch.randn(E, C, da, device=dev).bfloat16()
-    Cw = torch.randn(E, C, dg, device=dev).bfloat16()
-    D = torch.randn(E, C, do, device=dev).bfloat16()
+    g = torch.Generator().manual_seed(0)
+
+    def rand(*shape):
+        return torch.randn(*shape, generator=g).bfloat16().to(dev)
+
+    A, An = rand(E, C, da), rand(N, C, da)
+    B, Cw, D = rand(E, db), rand(E, C, dg), rand(E, C, do)
+    src = torch.randint(0, N, (E,), generator=g).to(dev)
+    dst = torch.randint(0, N, (E,), generator=g).sort().values
+    rowptr = torch.zeros(N + 1, dtype=torch.long)
+    rowptr[1:] = torch.bincount(dst, minlength=N).cumsum(0)
+    rowptr = rowptr.to(dev)
     ext = etp_mod.get_extension(required=True)
-    ent, coefs, _ = table.device_tensors(dev)
+    ent, coefs = table.device_tensors(dev)
 
-    def call():
-        return ext.etp_reduce(A, Cw, D, ent, coefs, db)
-
-    for _ in range(3):
-        call()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    iters = 20
-    for _ in range(iters):
-        call()
-    torch.cuda.synchronize()
-    us = (time.perf_counter() - t0) / iters * 1e6
-    gb = (A.numel() + Cw.numel() + D.numel()) * 2 / 1e9
-    print(f"block {block}: {us:8.1f} us  "
-          f"{gb / (us / 1e6):7.1f} GB/s  (read {gb:.2f} GB/call, "
-          f"dims da={da} db={db} dg={dg} do={do} "
-          f"n_ent={table.entries.shape[0]})")
+    row = 2 * C  # bytes of one bf16 (position, channel-row) per element
+    cases = {
+        "general": (
+            lambda: ext.etp_general(A, B, Cw, ent, coefs, do,
+                                    static_id=-1),
+            E * (row * (da + dg + do) + 2 * db)),
+        "reduce": (
+            lambda: ext.etp_reduce(A, Cw, D, ent, coefs, db),
+            E * (row * (da + dg + do) + 2 * db)),
+        "csr": (
+            lambda: ext.etp_nodesum(An, B, Cw, ent, coefs, do, rowptr,
+                                    src),
+            E * (row * (da + dg) + 2 * db) + N * row * do),
+    }
+    result = {"dims": [da, db, dg, do], "n_ent": table.entries.shape[0],
+              "E": E, "C": C, "reduce_block": reduce_block or 512}
+    for name, (call, nbytes) in cases.items():
+        us = median_us(call)
+        result[name + "_us"] = round(us, 1)
+        print(f"{name:8s} {us:8.1f} us  {nbytes / us / 1e3:7.1f} GB/s  "
+              f"({nbytes / 1e9:.2f} GB/call)")
+    print(json.dumps(result))
 
 
 if __name__ == "__main__":
-    run(int(sys.argv[1]) if len(sys.argv) > 1 else 256)
+    run(int(sys.argv[1]) if len(sys.argv) > 1 else None)

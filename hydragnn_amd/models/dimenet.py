@@ -18,7 +18,12 @@ import torch
 from torch import nn
 
 from ..ops import gather, get_edge_vectors_and_lengths, scatter
+from ..ops.gather_mul import SegmentPlan, fused_messages, gather_mul_sum
 from .base import Base
+
+# On unless HYDRAGNN_GATHER_MUL=0: dimenet_fp64 measured 1.2% faster
+# with the fused sums, and reproducible (profiles/README.md).
+FUSED_BY_DEFAULT = True
 from .pna_plus import BesselBasisLayer
 
 
@@ -150,11 +155,17 @@ class HydraEmbeddingBlock(nn.Module):
         self.lin = nn.Linear(3 * hidden, hidden)
         self.act = nn.SiLU()
 
-    def forward(self, x, rbf, edge_index):
+    def forward(self, x, rbf, edge_index, plans=None):
         src, dst = edge_index[0], edge_index[1]
         h = self.act(self.lin_x(x))
+        # with plans the two gathers' backward sums run in the plans'
+        # fixed order instead of by atomics
+        src_csr = dst_csr = None
+        if plans is not None and h.requires_grad:
+            src_csr, dst_csr = plans["src"].csr(), plans["dst"].csr()
         return self.act(self.lin(torch.cat(
-            [gather(h, src), gather(h, dst),
+            [gather(h, src, backward_csr=src_csr),
+             gather(h, dst, backward_csr=dst_csr),
              self.act(self.lin_rbf(rbf))], dim=-1)))
 
 
@@ -190,13 +201,19 @@ class InteractionPPBlock(nn.Module):
         self.after_skip = nn.ModuleList(
             [ResidualLayer(hidden) for _ in range(num_after_skip)])
 
-    def forward(self, m, rbf, sbf, idx_kj, idx_ji):
+    def forward(self, m, rbf, sbf, idx_kj, idx_ji, plans=None):
         x_ji = self.act(self.lin_ji(m))
         x_kj = self.act(self.lin_kj(m))
         x_kj = x_kj * self.lin_rbf2(self.lin_rbf1(rbf))
         x_kj = self.act(self.lin_down(x_kj))
-        x_kj = gather(x_kj, idx_kj) * self.lin_sbf2(self.lin_sbf1(sbf))
-        x_kj = scatter(x_kj, idx_ji, m.shape[0], "sum")
+        if plans is not None:
+            w = self.lin_sbf2(self.lin_sbf1(sbf))
+            dt = torch.promote_types(x_kj.dtype, w.dtype)
+            x_kj = gather_mul_sum(x_kj.to(dt), w.to(dt), plans["kj"],
+                                  plans["ji"])
+        else:
+            x_kj = gather(x_kj, idx_kj) * self.lin_sbf2(self.lin_sbf1(sbf))
+            x_kj = scatter(x_kj, idx_ji, m.shape[0], "sum")
         x_kj = self.act(self.lin_up(x_kj))
         h = x_ji + x_kj
         for layer in self.before_skip:
@@ -218,10 +235,16 @@ class OutputPPBlock(nn.Module):
                                    for _ in range(2)])
         self.lin_out = nn.Linear(out_emb, out_dim)
 
-    def forward(self, m, rbf, edge_index, num_nodes):
+    def forward(self, m, rbf, edge_index, num_nodes, plans=None):
         dst = edge_index[1]
-        w = self.lin_rbf(rbf) * m
-        x = scatter(w, dst, num_nodes, "sum")
+        if plans is not None:
+            w = self.lin_rbf(rbf)
+            dt = torch.promote_types(m.dtype, w.dtype)
+            x = gather_mul_sum(m.to(dt), w.to(dt), plans["edge"],
+                               plans["dst"])
+        else:
+            w = self.lin_rbf(rbf) * m
+            x = scatter(w, dst, num_nodes, "sum")
         x = self.lin_up(x)
         for lin in self.lins:
             x = self.act(lin(x))
@@ -239,11 +262,12 @@ class _DimeConv(nn.Module):
         self.output = OutputPPBlock(hidden, out_emb, out_dim, num_radial)
 
     def forward(self, inv_node_feat, equiv_node_feat, edge_index, rbf, sbf,
-                idx_kj, idx_ji, msg_state, **kwargs):
+                idx_kj, idx_ji, msg_state, gm_plans=None, **kwargs):
         m = msg_state["m"]
-        m = self.interaction(m, rbf, sbf, idx_kj, idx_ji)
+        m = self.interaction(m, rbf, sbf, idx_kj, idx_ji, gm_plans)
         msg_state["m"] = m
-        x = self.output(m, rbf, edge_index, inv_node_feat.shape[0])
+        x = self.output(m, rbf, edge_index, inv_node_feat.shape[0],
+                        gm_plans)
         return x, equiv_node_feat
 
 
@@ -297,11 +321,30 @@ class DIMEStack(Base):
         if not torch.is_floating_point(x):
             x = x.float()
         x = x.to(rbf.dtype)
-        m = self.emb_block(x, rbf, ei)
+        plans = None
+        if fused_messages(FUSED_BY_DEFAULT):
+            # one set of plans per batch, shared by every block: the
+            # triplet grouping (idx_ji ascends by construction in
+            # triplets(), idx_kj does not), the edge -> node groupings
+            # and the identity over the edges
+            n_edges = ei.shape[1]
+            plans = {
+                "kj": SegmentPlan.from_index(idx_kj, n_edges),
+                "ji": SegmentPlan.from_index(idx_ji, n_edges,
+                                             sorted_index=True),
+                "edge": SegmentPlan.identity(n_edges, ei.device),
+                "src": SegmentPlan.from_index(ei[0], data.num_nodes),
+                "dst": SegmentPlan.from_index(
+                    ei[1], data.num_nodes,
+                    sorted_index=getattr(self, "_edges_sorted", False)),
+            }
+        m = self.emb_block(x, rbf, ei, plans)
         conv_args = {
             "edge_index": ei, "rbf": rbf, "sbf": sbf,
             "idx_kj": idx_kj, "idx_ji": idx_ji, "msg_state": {"m": m},
         }
+        if plans is not None:
+            conv_args["gm_plans"] = plans
         return x, pos, conv_args
 
     def __str__(self):

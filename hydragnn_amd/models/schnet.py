@@ -23,7 +23,13 @@ from ..ops import (
     radius_graph,
     scatter,
 )
+from ..ops.gather_mul import SegmentPlan, fused_messages, gather_mul_sum
 from .base import Base
+
+# The fused CFConv message is off unless HYDRAGNN_GATHER_MUL=1: the op
+# alone is faster, but the schnet_mlip training step showed no gain (5%
+# slower in one session, level in another; profiles/README.md).
+FUSED_BY_DEFAULT = False
 
 
 class ShiftedSoftplus(nn.Module):
@@ -68,13 +74,24 @@ class CFConv(nn.Module):
             self.coord_nn = nn.Sequential(
                 nn.Linear(num_filters, num_filters), ShiftedSoftplus(), layer)
 
-    def forward(self, x, pos, edge_index, edge_shifts=None):
+    def forward(self, x, pos, edge_index, edge_shifts=None, plans=None):
+        """plans: the (src, dst) SegmentPlans of `edge_index` over the
+        nodes, for the fused message sum; None runs the composition.
+        The coordinate update needs the message per edge, so that
+        branch keeps the composition."""
         src, dst = edge_index[0], edge_index[1]
         vec, lengths = get_edge_vectors_and_lengths(pos, edge_index,
                                                     edge_shifts)
         d = lengths.squeeze(-1)
         W = self.filter_nn(self.smearing(d).to(x.dtype))
         W = W * cosine_cutoff(d, self.cutoff).view(-1, 1).to(x.dtype)
+        if plans is not None and not self.equivariant_coords:
+            h = self.lin1(x)
+            # under autocast the two sides can differ: promote, as the
+            # composition's product does
+            dt = torch.promote_types(h.dtype, W.dtype)
+            out = gather_mul_sum(h.to(dt), W.to(dt), plans[0], plans[1])
+            return self.lin2(out), pos
         msg = gather(self.lin1(x), src) * W
         if self.equivariant_coords:
             trans = vec.to(x.dtype) * self.coord_nn(msg)
@@ -96,16 +113,38 @@ class _SCFWrapper(nn.Module):
         self.max_neighbours = max_neighbours
         self.dynamic_graph = dynamic_graph
 
+    def _plans(self, edge_index, num_nodes, cache):
+        """One (src, dst) pair of plans per edge_index: the stack's
+        layers share `cache`, so the CSR of either side is built once
+        per batch."""
+        if cache is not None and "plans" in cache:
+            return cache["plans"]
+        plans = (SegmentPlan.from_index(edge_index[0], num_nodes),
+                 SegmentPlan.from_index(
+                     edge_index[1], num_nodes,
+                     sorted_index=getattr(self, "_edges_sorted", False)))
+        if cache is not None:
+            cache["plans"] = plans
+        return plans
+
     def forward(self, inv_node_feat, equiv_node_feat, edge_index,
-                edge_attr=None, edge_shifts=None, batch=None, **kwargs):
+                edge_attr=None, edge_shifts=None, batch=None,
+                plan_cache=None, **kwargs):
         if self.dynamic_graph and equiv_node_feat is not None and \
                 edge_shifts is None:
-            # rebuild the interaction graph from current coordinates
+            # rebuild the interaction graph from current coordinates;
+            # these edges are this layer's alone, and so are their plans
             edge_index = radius_graph(
                 equiv_node_feat.detach(), self.radius, batch=batch,
                 max_num_neighbors=self.max_neighbours)
+            plan_cache = None
+        plans = None
+        if fused_messages(FUSED_BY_DEFAULT) and \
+                not self.conv.equivariant_coords:
+            plans = self._plans(edge_index, inv_node_feat.shape[0],
+                                plan_cache)
         x, pos = self.conv(inv_node_feat, equiv_node_feat, edge_index,
-                           edge_shifts)
+                           edge_shifts, plans)
         return x, pos
 
 
@@ -134,6 +173,7 @@ class SCFStack(Base):
             "edge_index": data.edge_index,
             "edge_shifts": data.get("edge_shifts"),
             "batch": data.get("batch"),
+            "plan_cache": {},
         }
         x = data.x
         if x is not None and not torch.is_floating_point(x):

@@ -27,6 +27,7 @@ from .varlen_attn import varlen_attention
 from .segment_linear import segment_outer_sum, segment_matvec
 from .pna_aggr import (pna_aggregate, pna_scale, path_counts,
                        reset_path_counts)
+from .gather_mul import SegmentPlan, gather_mul_sum, gather_mul
 from .mfma_linear import MFMALinear
 from .splitk_linear import SplitKLinear
 
@@ -40,4 +41,5 @@ __all__ = [
     "irreps_linear", "varlen_attention", "MFMALinear", "SplitKLinear",
     "segment_outer_sum", "segment_matvec",
     "pna_aggregate", "pna_scale", "path_counts", "reset_path_counts",
+    "SegmentPlan", "gather_mul_sum", "gather_mul",
 ]

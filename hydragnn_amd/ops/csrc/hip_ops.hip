@@ -767,7 +767,26 @@ std::vector<torch::Tensor> pna_bwd2(torch::Tensor x, torch::Tensor rowptr,
                                     bool need_G, bool need_x);
 long pna_grid_blocks(long n_threads);
 
+// defined in gather_mul.hip
+torch::Tensor gather_mul_sum(torch::Tensor x, torch::Tensor w,
+                             c10::optional<torch::Tensor> gidx,
+                             torch::Tensor rowptr,
+                             c10::optional<torch::Tensor> perm);
+torch::Tensor gather_mul(torch::Tensor a, torch::Tensor b,
+                         c10::optional<torch::Tensor> ia,
+                         c10::optional<torch::Tensor> ib, long E);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("gather_mul_sum", &gather_mul_sum,
+        "out[i] = sum over CSR row i of x[gidx[e]] * w[e] (HIP); an "
+        "absent gidx is the identity",
+        pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("gidx"),
+        pybind11::arg("rowptr"), pybind11::arg("perm"));
+  m.def("gather_mul", &gather_mul,
+        "out[e] = a[ia[e]] * b[ib[e]] (HIP); an absent index is the "
+        "identity",
+        pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("ia"),
+        pybind11::arg("ib"), pybind11::arg("E"));
   m.def("pna_fwd", &pna_fwd,
         "fused PNA aggregation -> (out, stats, arg) (HIP); aggregator "
         "ids: 0 sum, 1 mean, 2 min, 3 max, 4 std, 5 var",

@@ -3,7 +3,10 @@ multi-head QM9-shape, EGNN + GPS global attention, DimeNet fp64 with
 gradient checkpointing on periodic cells; and the PNA family: PNAEq as
 an MLIP (energy + forces, double backward) and PNAPlus on QM9-shaped
 molecules, both through DegreeScalerAggregation (HYDRAGNN_PNA_FUSED=0
-times the composition instead).  The driver's contract bench
+times the composition instead); and SchNet as an MLIP on the same
+MD17-shaped molecules, through the fused gather-multiply-sum
+(HYDRAGNN_GATHER_MUL=0 times the composition; this also switches
+dimenet_fp64).  The driver's contract bench
 (bench.py) stays MACE; this script produces the per-config evidence
 lines.
 
@@ -101,6 +104,18 @@ CONFIGS = {
                    output_heads=_NODE_HEAD, task_weights=[1.0],
                    num_conv_layers=3, radius=5.0, num_radial=20,
                    max_neighbours=32, equivariance=True,
+                   activation_function="silu",
+                   enable_interatomic_potential=True, energy_weight=1.0,
+                   energy_peratom_weight=0.0, force_weight=10.0)),
+    "schnet_mlip": dict(
+        label="SchNet MLIP energy+forces, MD17-shape, fp32",
+        precision="fp32", local_batch=256, mlip=True,
+        data=md17_shape,
+        model=dict(mpnn_type="SchNet", input_dim=1, hidden_dim=64,
+                   output_dim=[1], output_type=["node"],
+                   output_heads=_NODE_HEAD, task_weights=[1.0],
+                   num_conv_layers=3, radius=5.0, num_gaussians=50,
+                   num_filters=64, max_neighbours=32,
                    activation_function="silu",
                    enable_interatomic_potential=True, energy_weight=1.0,
                    energy_peratom_weight=0.0, force_weight=10.0)),

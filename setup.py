@@ -20,7 +20,8 @@ ext_modules = [
                  "hydragnn_amd/ops/csrc/irreps_linear.hip",
                  "hydragnn_amd/ops/csrc/symcon.hip",
                  "hydragnn_amd/ops/csrc/segment_linear.hip",
-                 "hydragnn_amd/ops/csrc/pna_aggr.hip"],
+                 "hydragnn_amd/ops/csrc/pna_aggr.hip",
+                 "hydragnn_amd/ops/csrc/gather_mul.hip"],
         extra_compile_args={
             "cxx": ["-O3"],
             "nvcc": ["-O3", "--offload-arch=gfx950"],

@@ -177,8 +177,10 @@ namespace {
 
 // Cell-list pair enumeration for LARGE graphs (10k+ atoms, open
 // boundary): atoms pre-sorted by cell id (host does the argsort),
-// cells are cubes of edge r; each atom scans the 27 neighbor cells'
-// contiguous atom ranges.  O(N * 27 * atoms/cell) instead of O(N^2).
+// cells are cubes of edge slightly above r (the host states the margin
+// that keeps every accepted pair at most one cell apart); each atom
+// scans the 27 neighbor cells' contiguous atom ranges.
+// O(N * 27 * atoms/cell) instead of O(N^2).
 template <typename T>
 __global__ __launch_bounds__(RB) void radius_cells_kernel(
     const T* __restrict__ pos,          // [N, 3] (original order)

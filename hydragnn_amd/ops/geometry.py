@@ -65,17 +65,21 @@ def _radius_graph_torch(
     n = pos.shape[0]
     if n == 0:
         return torch.zeros(2, 0, dtype=torch.long, device=pos.device)
-    d = torch.cdist(pos, pos)
-    mask = d <= r
+    # squared distances from differences, in the position dtype, as
+    # the HIP kernels do: translation invariant where the differences
+    # are exact (torch.cdist's matmul form |x|^2+|y|^2-2xy is not)
+    diff = pos.unsqueeze(0) - pos.unsqueeze(1)
+    d2 = (diff * diff).sum(-1)
+    mask = d2 <= torch.tensor(r * r, dtype=pos.dtype, device=pos.device)
     if not loop:
         mask.fill_diagonal_(False)
     if batch is not None:
         mask &= batch.view(-1, 1) == batch.view(1, -1)
     if max_num_neighbors < n:
         # keep the max_num_neighbors closest sources per destination
-        d_masked = torch.where(mask, d, torch.full_like(d, float("inf")))
-        k = min(max_num_neighbors, n)
-        _, idx = torch.topk(d_masked, k, dim=1, largest=False)
+        d_masked = torch.where(mask, d2, torch.full_like(d2, float("inf")))
+        _, idx = torch.topk(d_masked, max_num_neighbors, dim=1,
+                            largest=False)
         keep = torch.zeros_like(mask)
         keep.scatter_(1, idx, True)
         mask &= keep
@@ -102,7 +106,12 @@ def radius_graph(
             # O(N * 27 * atoms/cell) instead of the tiled O(N^2)
             res = _radius_pairs_cell_list(pos, r, loop)
             if res is not None:
-                return _cap_and_stack(*res, n, max_num_neighbors)
+                # the kernel's edges follow the cell sort
+                src, dst, dist = res
+                sel = (_closest_k(dst, dist, n, max_num_neighbors)
+                       if max_num_neighbors < n
+                       else torch.argsort(dst, stable=True))
+                return torch.stack([src[sel], dst[sel]], dim=0)
         if batch is None:
             batch_t = torch.zeros(n, dtype=torch.long, device=pos.device)
             gptr = torch.tensor([0, n], dtype=torch.long, device=pos.device)
@@ -119,36 +128,61 @@ def radius_graph(
             p = p.float()
         src, dst, dist, _ = ext.radius_pairs_t(
             p, batch_t, gptr, float(r), bool(loop))
-        if max_num_neighbors < n and dst.numel() > 0:
-            # cap: keep the max_num_neighbors closest srcs per dst
-            order = torch.argsort(dst * (dist.max() + 1.0) + dist)
-            src, dst, dist = src[order], dst[order], dist[order]
-            counts = torch.bincount(dst, minlength=n)
-            seg_start = torch.zeros(n, dtype=torch.long, device=pos.device)
-            seg_start[1:] = counts.cumsum(0)[:-1]
-            pos_in_seg = (
-                torch.arange(dst.numel(), device=pos.device)
-                - seg_start[dst])
-            keep = pos_in_seg < max_num_neighbors
-            src, dst = src[keep], dst[keep]
+        if max_num_neighbors < n:
+            sel = _closest_k(dst, dist, n, max_num_neighbors)
+            src, dst = src[sel], dst[sel]
         return torch.stack([src, dst], dim=0)
     return _radius_graph_torch(pos, r, batch, max_num_neighbors, loop)
 
 
-# ---------------------------------------------------------------------------
-# Periodic (PBC) radius graph — preprocessing-time, CPU/numpy
-# ---------------------------------------------------------------------------
+def _closest_k(dst, dist, n, k):
+    """Indices of the edges to keep under a cap of k per destination,
+    dst-major and by ascending distance within a destination: the k
+    closest, any choice among equal distances.
+
+    Two stable sorts, by distance and then by destination.  (A single
+    float key dst * (dist.max() + 1) + dist has an ulp that grows with
+    the destination index and merges distinct distances.)"""
+    order = torch.argsort(dist, stable=True)
+    order = order[torch.argsort(dst[order], stable=True)]
+    dst = dst[order]
+    counts = torch.bincount(dst, minlength=n)
+    seg_start = counts.cumsum(0) - counts
+    pos_in_seg = torch.arange(dst.numel(), device=dst.device) \
+        - seg_start[dst]
+    return order[pos_in_seg < k]
+
+
+# cell edge of the cell list, in units of the cutoff
+_CELL_EDGE = 1.0 + 2.0 ** -10
+
+
 def _radius_pairs_cell_list(pos, r, loop):
     """Cell-list pair enumeration for one large open-boundary graph:
     host side computes the cell binning (argsort by cell id), the HIP
     kernel scans each atom's 27 neighbor cells (SURVEY §2c radius-graph
-    row: 'cell binning + pair enumeration')."""
+    row: 'cell binning + pair enumeration').
+
+    The scan is complete only if every pair the kernel accepts is at
+    most one cell apart per axis.  The kernel accepts fl(d2) <= fl(r2)
+    in the position dtype (eps = 2^-23 or 2^-52): a difference, three
+    products and two sums of non-negative terms put the true
+    per-axis separation below r (1 + 4 eps).  The bins are
+    floor((x - lo) / edge) in fp64 whatever the position dtype, so with
+    T cells along the axis each quotient is within 3 * 2^-53 * T of
+    its true value, and two bins differ by at most one while
+        r (1 + 4 eps) / edge + 6 * 2^-53 * T < 1.
+    edge = r (1 + 2^-10) makes the first term 1 - 9.7e-4 + 4 eps, so
+    the inequality holds for every T a cell table can have (T < 10^12).
+    Neither an edge of exactly r nor bins taken in fp32 leave such a
+    margin."""
     ext = get_extension(required=True)
     p = pos.detach().contiguous()
     if p.dtype not in (torch.float32, torch.float64):
         p = p.float()
-    lo = p.min(dim=0).values
-    cell_idx = ((p - lo) / r).floor().long()        # [N, 3]
+    p64 = p.double()
+    lo = p64.min(dim=0).values
+    cell_idx = ((p64 - lo) / (r * _CELL_EDGE)).floor().long()   # [N, 3]
     ncell = cell_idx.max(dim=0).values + 1          # [3]
     ncx, ncy, ncz = (int(ncell[0]), int(ncell[1]), int(ncell[2]))
     n_cells = ncx * ncy * ncz
@@ -169,23 +203,42 @@ def _radius_pairs_cell_list(pos, r, loop):
     return src, dst, dist
 
 
-def _cap_and_stack(src, dst, dist, n, max_num_neighbors):
-    """dst-major sort + per-dst closest-k cap (shared tail of the
-    radius paths)."""
-    if dst.numel() == 0:
-        return torch.stack([src, dst], dim=0)
-    order = torch.argsort(dst * (dist.max() + 1.0) + dist)
-    src, dst, dist = src[order], dst[order], dist[order]
-    if max_num_neighbors < n:
-        counts = torch.bincount(dst, minlength=n)
-        seg_start = torch.zeros(n, dtype=torch.long,
-                                device=dst.device)
-        seg_start[1:] = counts.cumsum(0)[:-1]
-        pos_in_seg = (torch.arange(dst.numel(), device=dst.device)
-                      - seg_start[dst])
-        keep = pos_in_seg < max_num_neighbors
-        src, dst = src[keep], dst[keep]
-    return torch.stack([src, dst], dim=0)
+# ---------------------------------------------------------------------------
+# Periodic (PBC) radius graph: numpy on the CPU, tiled HIP kernel on GPU
+# ---------------------------------------------------------------------------
+def _pbc_images(p, c, pbc, r):
+    """Host side of both periodic paths, in fp64 numpy.
+
+    Returns (wrap [n, 3] int64, shifts_int [S, 3] int64).  Atom a is
+    searched at p[a] - wrap[a] @ c, which lies in the unit cell along
+    every periodic direction, so positions may be unwrapped; an edge
+    found there with image S' has the shift S' - wrap[dst] + wrap[src]
+    on the positions as given.
+
+    Images per periodic direction i: an edge has |f_dst - f_src + S'|_i
+    * h_i <= r, with f the wrapped fractional coordinates and h_i = V /
+    |a_j x a_k| the cell's perpendicular width, so |S'_i| <= r / h_i +
+    spread_i, where spread_i = max f_i - min f_i < 1.  The 1e-6 covers
+    the rounding of f and r / h; a spare image costs time only."""
+    n = p.shape[0]
+    wrap = np.zeros((n, 3), dtype=np.int64)
+    n_img = np.zeros(3, dtype=int)
+    vol = abs(np.linalg.det(c))
+    if vol > 0:
+        frac = p @ np.linalg.inv(c)
+        wrap[:, pbc] = np.floor(frac[:, pbc]).astype(np.int64)
+        frac = frac - wrap
+        spread = frac.max(axis=0) - frac.min(axis=0)
+        for i in range(3):
+            if not pbc[i]:
+                continue
+            j, k = (i + 1) % 3, (i + 2) % 3
+            h = vol / np.linalg.norm(np.cross(c[j], c[k]))
+            n_img[i] = int(math.floor(r / h + spread[i] + 1e-6))
+    grids = np.meshgrid(*[np.arange(-n_img[i], n_img[i] + 1)
+                          for i in range(3)], indexing="ij")
+    shifts_int = np.stack([g.ravel() for g in grids], axis=1)
+    return wrap, shifts_int.astype(np.int64)
 
 
 def radius_graph_pbc(
@@ -204,7 +257,8 @@ def radius_graph_pbc(
     updates.py:172) with an explicit image enumeration: number of images
     per lattice direction chosen from the cell's perpendicular widths so
     a cutoff larger than the box is still correct; mixed PBC simply
-    zeroes the non-periodic directions.
+    zeroes the non-periodic directions.  Positions may lie outside the
+    cell (unwrapped trajectories): see `_pbc_images`.
     """
     device = pos.device
     dtype = pos.dtype
@@ -219,36 +273,17 @@ def radius_graph_pbc(
         return (torch.zeros(2, 0, dtype=torch.long, device=device),
                 torch.zeros(0, 3, dtype=dtype, device=device))
 
-    # Perpendicular width of the cell along each lattice direction:
-    # h_i = V / |a_j x a_k| ; images needed: ceil(r / h_i).
-    vol = abs(np.linalg.det(c))
-    n_img = np.zeros(3, dtype=int)
-    for i in range(3):
-        if not pbc[i]:
-            continue
-        j, k = (i + 1) % 3, (i + 2) % 3
-        cross = np.cross(c[j], c[k])
-        area = np.linalg.norm(cross)
-        h = vol / area if area > 0 else np.inf
-        n_img[i] = int(math.ceil(r / h)) if h > 0 and np.isfinite(h) else 0
-
-    shifts_int = []
-    ranges = [range(-n_img[i], n_img[i] + 1) for i in range(3)]
-    for sx in ranges[0]:
-        for sy in ranges[1]:
-            for sz in ranges[2]:
-                shifts_int.append((sx, sy, sz))
-    shifts_int = np.array(shifts_int, dtype=np.float64)  # [S,3]
+    wrap, shifts_int = _pbc_images(p, c, pbc, r)
+    p = p - wrap @ c
     shift_cart = shifts_int @ c  # [S,3]
 
-    src_list, dst_list, sh_list = [], [], []
+    # Convention: edge (src=i, dst=j) with image S' means
+    # vec = p[j] - p[i] + S' @ cell on the wrapped positions.
+    src_list, dst_list, img_list = [], [], []
     r2 = r * r
     for s_idx in range(shift_cart.shape[0]):
         sh = shift_cart[s_idx]
-        is_zero = np.all(shifts_int[s_idx] == 0)
-        # d[i,j] = |p[j] + sh - p[i]|  (edge i->j means vector p[j]-p[i]+(-sh)?)
-        # Convention: edge (src=i, dst=j) with shift S means
-        # vec = p[j] - p[i] + S@cell. Enumerate all i,j pairs.
+        is_zero = not shifts_int[s_idx].any()
         diff = p[None, :, :] + sh[None, None, :] - p[:, None, :]  # [i,j,3]
         d2 = np.einsum("ijk,ijk->ij", diff, diff)
         m = d2 <= r2
@@ -258,7 +293,7 @@ def radius_graph_pbc(
         if ii.size:
             src_list.append(ii)
             dst_list.append(jj)
-            sh_list.append(np.repeat(sh[None, :], ii.size, axis=0))
+            img_list.append(np.full(ii.size, s_idx))
 
     if not src_list:
         return (torch.zeros(2, 0, dtype=torch.long, device=device),
@@ -266,28 +301,22 @@ def radius_graph_pbc(
 
     src = np.concatenate(src_list)
     dst = np.concatenate(dst_list)
-    sh = np.concatenate(sh_list)
+    img = np.concatenate(img_list)
 
-    # Edge convention: (src -> dst): vec = p[dst] - p[src] + shift.
-    # Above we computed p[j] + sh - p[i] for pair (i, j) => src=i, dst=j,
-    # shift=sh. Good.
-
-    if max_num_neighbors < n * 27:
-        # cap neighbors per dst by distance order (lexsort (dst, length))
-        vec = p[dst] - p[src] + sh
-        length = np.sqrt(np.einsum("ij,ij->i", vec, vec))
-        order = np.lexsort((length, dst))
-        src, dst, sh = src[order], dst[order], sh[order]
+    if np.any(np.bincount(dst, minlength=n) > max_num_neighbors):
+        # cap neighbors per dst by distance order (lexsort (dst, d2))
+        vec = p[dst] - p[src] + shift_cart[img]
+        order = np.lexsort((np.einsum("ij,ij->i", vec, vec), dst))
+        src, dst, img = src[order], dst[order], img[order]
         counts = np.bincount(dst, minlength=n)
-        keep = np.ones(len(dst), dtype=bool)
-        if np.any(counts > max_num_neighbors):
-            pos_in_seg = np.arange(len(dst)) - np.concatenate(
-                ([0], np.cumsum(counts)[:-1]))[dst]
-            keep = pos_in_seg < max_num_neighbors
-        src, dst, sh = src[keep], dst[keep], sh[keep]
+        pos_in_seg = np.arange(len(dst)) - (np.cumsum(counts) - counts)[dst]
+        keep = pos_in_seg < max_num_neighbors
+        src, dst, img = src[keep], dst[keep], img[keep]
 
     order = np.lexsort((src, dst))  # dst-major for the CSR fast path
-    src, dst, sh = src[order], dst[order], sh[order]
+    src, dst, img = src[order], dst[order], img[order]
+    # shifts on the positions as given
+    sh = (shifts_int[img] - wrap[dst] + wrap[src]) @ c
     edge_index = torch.from_numpy(np.stack([src, dst])).long().to(device)
     edge_shifts = torch.from_numpy(sh).to(dtype).to(device)
     return edge_index, edge_shifts
@@ -306,45 +335,27 @@ def _radius_graph_pbc_hip(pos, r, cell, pbc, max_num_neighbors, loop):
                 torch.zeros(0, 3, dtype=dtype, device=device))
     c = cell.detach().cpu().double().numpy().reshape(3, 3)
     pbc_arr = np.asarray(pbc, dtype=bool).reshape(3)
-    vol = abs(np.linalg.det(c))
-    n_img = np.zeros(3, dtype=int)
-    for i in range(3):
-        if not pbc_arr[i]:
-            continue
-        j, k = (i + 1) % 3, (i + 2) % 3
-        cross = np.cross(c[j], c[k])
-        area = np.linalg.norm(cross)
-        h = vol / area if area > 0 else np.inf
-        n_img[i] = int(math.ceil(r / h)) if h > 0 and np.isfinite(h) \
-            else 0
-    grids = np.meshgrid(*[np.arange(-n_img[i], n_img[i] + 1)
-                          for i in range(3)], indexing="ij")
-    shifts_int = np.stack([g.ravel() for g in grids],
-                          axis=1).astype(np.float64)      # [S, 3]
-    shift_cart = shifts_int @ c                            # [S, 3]
-    p = pos.detach().contiguous()
-    if p.dtype not in (torch.float32, torch.float64):
-        p = p.double()
+    wrap, shifts_int = _pbc_images(
+        pos.detach().cpu().double().numpy(), c, pbc_arr, r)
+    kdtype = dtype if dtype in (torch.float32, torch.float64) \
+        else torch.float64
+    c_dev = torch.from_numpy(c).to(device)
+    wrap = torch.from_numpy(wrap).to(device)
+    shifts_int = torch.from_numpy(shifts_int).to(device)
+    # wrapped positions, rounded once to the kernel's dtype (unchanged
+    # where the atom already lies in the cell)
+    p = (pos.detach().double() - wrap.double() @ c_dev).to(kdtype)
     # kernel convention: membership |p[src] + s - p[dst]| <= r; the
     # edge convention vec = p[dst] - p[src] + shift  =>  shift = -s
-    sh_dev = torch.from_numpy(shift_cart).to(device=device,
-                                             dtype=p.dtype)
+    sh_dev = (shifts_int.double() @ c_dev).to(kdtype)
     batch_t = torch.zeros(n, dtype=torch.long, device=device)
     gptr = torch.tensor([0, n], dtype=torch.long, device=device)
     src, dst, dist, simg = ext.radius_pairs_t(
         p, batch_t, gptr, float(r), bool(loop), sh_dev)
-    edge_shifts = -sh_dev[simg]
-    if max_num_neighbors < n * max(1, sh_dev.shape[0]) \
-            and dst.numel() > 0:
-        order = torch.argsort(dst * (dist.max() + 1.0) + dist)
-        src, dst, edge_shifts = src[order], dst[order], \
-            edge_shifts[order]
-        counts = torch.bincount(dst, minlength=n)
-        seg_start = torch.zeros(n, dtype=torch.long, device=device)
-        seg_start[1:] = counts.cumsum(0)[:-1]
-        pos_in_seg = (torch.arange(dst.numel(), device=device)
-                      - seg_start[dst])
-        keep = pos_in_seg < max_num_neighbors
-        src, dst, edge_shifts = src[keep], dst[keep], edge_shifts[keep]
-    return (torch.stack([src, dst], dim=0),
-            edge_shifts.to(dtype))
+    if max_num_neighbors < n * sh_dev.shape[0]:
+        sel = _closest_k(dst, dist, n, max_num_neighbors)
+        src, dst, simg = src[sel], dst[sel], simg[sel]
+    # integer shifts on the positions as given
+    s_int = wrap[src] - wrap[dst] - shifts_int[simg]
+    edge_shifts = (s_int.double() @ c_dev).to(dtype)
+    return torch.stack([src, dst], dim=0), edge_shifts

@@ -204,8 +204,28 @@ class RealAgnosticResidualInteractionBlock(nn.Module):
     def _setup_extra(self, num_channels: int):
         pass
 
+    def _radial_tail(self, h: torch.Tensor) -> torch.Tensor:
+        """radial_mlp[1:] on the first layer's pre-activation h: each
+        SiLU -> Linear pair that qualifies runs as one fused act_linear
+        (ops/act_linear.py), the others as the modules themselves."""
+        from ...ops import act_linear as al
+        tail = self.radial_mlp[1:]
+        if not (al.fused_route() and h.dim() == 2 and h.is_cuda
+                and h.dtype == torch.bfloat16 and not al.use_eager()
+                and len(tail) % 2 == 0):
+            return tail(h)
+        for act, lin in zip(tail[0::2], tail[1::2]):
+            if (type(act) is nn.SiLU and isinstance(lin, nn.Linear)
+                    and lin.weight.dtype == torch.bfloat16
+                    and al.in_envelope(h.shape[0], lin.out_features,
+                                       lin.in_features)):
+                h = al.act_linear(h, lin.weight, lin.bias)
+            else:
+                h = lin(act(h))
+        return h
+
     def _edge_weights(self, node_feats, src, dst, edge_radial, etp_meta):
-        return self.radial_mlp(edge_radial)
+        return self._radial_tail(self.radial_mlp[0](edge_radial))
 
     def forward(self, node_feats: torch.Tensor, edge_index: torch.Tensor,
                 edge_sh: torch.Tensor, edge_radial: torch.Tensor,
@@ -294,7 +314,7 @@ class RealAgnosticAttResidualInteractionBlock(
             h_d = torch.nn.functional.linear(down, W1[:, rd + c:])
         h = h + gather(h_s, src, backward_csr=src_csr) \
             + gather(h_d, dst, backward_csr=dst_csr)
-        return self.radial_mlp[1:](h)
+        return self._radial_tail(h)
 
 
 class EquivariantProductBasisBlock(nn.Module):

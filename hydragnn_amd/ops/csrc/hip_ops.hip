@@ -776,7 +776,43 @@ torch::Tensor gather_mul(torch::Tensor a, torch::Tensor b,
                          c10::optional<torch::Tensor> ia,
                          c10::optional<torch::Tensor> ib, long E);
 
+// defined in act_linear.hip
+torch::Tensor act_linear_fwd(torch::Tensor h, torch::Tensor W,
+                             c10::optional<torch::Tensor> bias);
+torch::Tensor act_linear_dgrad(torch::Tensor g, torch::Tensor W,
+                               torch::Tensor h);
+torch::Tensor act_linear_dgrad_dg(torch::Tensor u, torch::Tensor W,
+                                  torch::Tensor h);
+torch::Tensor act_linear_dgrad_dh(torch::Tensor u, torch::Tensor g,
+                                  torch::Tensor W, torch::Tensor h);
+std::vector<torch::Tensor> act_linear_wgrad(
+    torch::Tensor g, torch::Tensor x, c10::optional<torch::Tensor> u,
+    bool act, bool want_bias);
+long act_linear_wgrad_chunks(long E);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("act_linear_fwd", &act_linear_fwd,
+        "y = bf16(silu(h)) W^T + b (HIP)",
+        pybind11::arg("h"), pybind11::arg("W"),
+        pybind11::arg("bias") = pybind11::none());
+  m.def("act_linear_dgrad", &act_linear_dgrad,
+        "gh = (g W) silu'(h) (HIP)",
+        pybind11::arg("g"), pybind11::arg("W"), pybind11::arg("h"));
+  m.def("act_linear_dgrad_dg", &act_linear_dgrad_dg,
+        "dg = bf16(u silu'(h)) W^T (HIP)",
+        pybind11::arg("u"), pybind11::arg("W"), pybind11::arg("h"));
+  m.def("act_linear_dgrad_dh", &act_linear_dgrad_dh,
+        "dh = u (g W) silu''(h) (HIP)",
+        pybind11::arg("u"), pybind11::arg("g"), pybind11::arg("W"),
+        pybind11::arg("h"));
+  m.def("act_linear_wgrad", &act_linear_wgrad,
+        "(gW, gb) = (g^T p, column sum of g), p = x, bf16(silu(x)) or "
+        "bf16(u silu'(x)) (HIP)",
+        pybind11::arg("g"), pybind11::arg("x"),
+        pybind11::arg("u") = pybind11::none(),
+        pybind11::arg("act") = true, pybind11::arg("want_bias") = false);
+  m.def("act_linear_wgrad_chunks", &act_linear_wgrad_chunks,
+        "E-chunks of an act_linear_wgrad launch: a function of E alone");
   m.def("gather_mul_sum", &gather_mul_sum,
         "out[i] = sum over CSR row i of x[gidx[e]] * w[e] (HIP); an "
         "absent gidx is the identity",

@@ -21,7 +21,8 @@ ext_modules = [
                  "hydragnn_amd/ops/csrc/symcon.hip",
                  "hydragnn_amd/ops/csrc/segment_linear.hip",
                  "hydragnn_amd/ops/csrc/pna_aggr.hip",
-                 "hydragnn_amd/ops/csrc/gather_mul.hip"],
+                 "hydragnn_amd/ops/csrc/gather_mul.hip",
+                 "hydragnn_amd/ops/csrc/act_linear.hip"],
         extra_compile_args={
             "cxx": ["-O3"],
             "nvcc": ["-O3", "--offload-arch=gfx950"],

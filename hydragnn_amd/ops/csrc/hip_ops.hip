@@ -707,13 +707,14 @@ torch::Tensor gemv_small_n(torch::Tensor A, torch::Tensor W,
                            c10::optional<torch::Tensor> bias);
 // defined in fused_adamw.hip
 void fused_adamw(torch::Tensor p, torch::Tensor g, torch::Tensor m,
-                 torch::Tensor v, torch::Tensor step, double lr,
-                 double beta1, double beta2, double eps, double wd);
+                 torch::Tensor v, torch::Tensor step, torch::Tensor bc,
+                 double lr, double beta1, double beta2, double eps,
+                 double wd);
 void fused_adamw_bf16(torch::Tensor p, torch::Tensor g,
                       torch::Tensor master, torch::Tensor m,
-                      torch::Tensor v, torch::Tensor step, double lr,
-                      double beta1, double beta2, double eps,
-                      double wd);
+                      torch::Tensor v, torch::Tensor step,
+                      torch::Tensor bc, double lr, double beta1,
+                      double beta2, double eps, double wd);
 // defined in radius.hip
 std::vector<torch::Tensor> radius_pairs_t(torch::Tensor pos,
                                           torch::Tensor batch,

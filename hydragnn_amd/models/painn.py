@@ -21,8 +21,31 @@ from ..ops import (
     scatter,
     sinc_basis,
 )
+from ..ops.gather_mul import SegmentPlan
 from ..ops.mfma_linear import MFMALinear
+from ..ops.painn_message import fused_painn, painn_message
 from .base import Base
+
+# the unset default of HYDRAGNN_PAINN_FUSED for this stack, from the
+# end-to-end step (profiles/README.md)
+FUSED_BY_DEFAULT = False
+
+
+def common_dtype(*tensors):
+    """The operands in their promoted dtype: under autocast the gate MLP
+    and the filter can differ, and the composition's products promote."""
+    dt = tensors[0].dtype
+    for t in tensors[1:]:
+        dt = torch.promote_types(dt, t.dtype)
+    return [t.to(dt) for t in tensors]
+
+
+def message_plans(edge_index, num_nodes, edges_sorted):
+    """The (src, dst) SegmentPlans of one batch's edges over its nodes,
+    shared by every layer of a stack."""
+    return (SegmentPlan.from_index(edge_index[0], num_nodes),
+            SegmentPlan.from_index(edge_index[1], num_nodes,
+                                   sorted_index=edges_sorted))
 
 
 class PainnMessage(nn.Module):
@@ -37,12 +60,23 @@ class PainnMessage(nn.Module):
         self.filter_layer = nn.Linear(num_radial, node_size * 3)
 
     def forward(self, node_scalar, node_vector, edge_index, edge_diff,
-                edge_dist):
+                edge_dist, plans=None):
+        """plans: the (src, dst) SegmentPlans of `edge_index` over the
+        nodes, for the fused message; None runs the composition."""
         src, dst = edge_index[0], edge_index[1]
         rbf = sinc_basis(edge_dist, self.cutoff, self.num_radial)
         filter_weight = self.filter_layer(rbf.to(node_scalar.dtype))
         filter_weight = filter_weight * cosine_cutoff(
             edge_dist, self.cutoff).to(node_scalar.dtype)
+        if plans is not None:
+            unit = (edge_diff / edge_dist.clamp(min=1e-9)).to(
+                node_scalar.dtype)
+            residual_scalar, residual_vector = painn_message(
+                *common_dtype(self.scalar_message_mlp(node_scalar),
+                              filter_weight, node_vector, unit),
+                plans[0], plans[1])
+            return (node_scalar + residual_scalar,
+                    node_vector + residual_vector)
         scalar_out = gather(self.scalar_message_mlp(node_scalar), src)
         filter_out = filter_weight * scalar_out
         gate_state_vector, gate_edge_vector, message_scalar = torch.split(
@@ -105,11 +139,13 @@ class _PainnConv(nn.Module):
                               if in_size != out_size else nn.Identity())
 
     def forward(self, inv_node_feat, equiv_node_feat, edge_index,
-                edge_diff, edge_dist, node_vector=None, **kwargs):
+                edge_diff, edge_dist, node_vector=None, plans=None,
+                **kwargs):
         s = inv_node_feat
         if node_vector is None or node_vector.shape[-1] != self.in_size:
             node_vector = s.new_zeros(s.shape[0], 3, self.in_size)
-        s, v = self.message(s, node_vector, edge_index, edge_diff, edge_dist)
+        s, v = self.message(s, node_vector, edge_index, edge_diff, edge_dist,
+                            plans)
         s, v = self.update(s, v)
         s = self.node_embed_out(s)
         v = self.vec_embed_out(v)
@@ -124,10 +160,10 @@ class _PainnWrapper(nn.Module):
         self.conv = conv
 
     def forward(self, inv_node_feat, equiv_node_feat, edge_index,
-                edge_diff, edge_dist, vec_state, **kwargs):
+                edge_diff, edge_dist, vec_state, plans=None, **kwargs):
         s, v = self.conv(inv_node_feat, equiv_node_feat, edge_index,
                          edge_diff, edge_dist,
-                         node_vector=vec_state.get("v"))
+                         node_vector=vec_state.get("v"), plans=plans)
         vec_state["v"] = v
         return s, equiv_node_feat
 
@@ -167,6 +203,10 @@ class PAINNStack(Base):
             "edge_dist": edge_dist,
             "vec_state": {},
         }
+        if fused_painn(FUSED_BY_DEFAULT):
+            conv_args["plans"] = message_plans(
+                data.edge_index, x.shape[0],
+                getattr(self, "_edges_sorted", False))
         if self.use_global_attn:
             conv_args["batch"] = data.get("batch")
         return x, data.pos, conv_args

@@ -21,9 +21,14 @@ from ..ops import (
     sinc_basis,
 )
 from ..ops.mfma_linear import MFMALinear
+from ..ops.painn_message import fused_painn, painn_message
 from .base import Base, BatchNormNode
 from .layers import DegreeScalerAggregation
-from .painn import PainnUpdate
+from .painn import PainnUpdate, common_dtype, message_plans
+
+# the unset default of HYDRAGNN_PAINN_FUSED for this stack, from the
+# end-to-end step (profiles/README.md)
+FUSED_BY_DEFAULT = False
 
 
 class PNAEqMessage(nn.Module):
@@ -43,11 +48,27 @@ class PNAEqMessage(nn.Module):
             node_size * len(aggregators) * len(scalers), node_size)
 
     def forward(self, node_scalar, node_vector, edge_index, edge_diff,
-                edge_dist):
+                edge_dist, plans=None):
+        """plans: the (src, dst) SegmentPlans of `edge_index` over the
+        nodes, for the fused vector message; None runs the composition.
+        The scalar message goes per edge into the degree-scaler
+        aggregation either way."""
         src, dst = edge_index[0], edge_index[1]
         rbf = sinc_basis(edge_dist, self.cutoff, self.num_radial)
         fw = self.filter_layer(rbf.to(node_scalar.dtype))
         fw = fw * cosine_cutoff(edge_dist, self.cutoff).to(node_scalar.dtype)
+        if plans is not None:
+            phi = self.scalar_message_mlp(node_scalar)
+            unit = (edge_diff / edge_dist.clamp(min=1e-9)).to(
+                node_scalar.dtype)
+            _, res_v = painn_message(
+                *common_dtype(phi, fw, node_vector, unit), plans[0],
+                plans[1], scalar=False)
+            f2 = 2 * self.node_size
+            msg_s = fw[:, f2:] * gather(phi[:, f2:], src)
+            res_s = self.scalar_proj(
+                self.aggr(msg_s, dst, node_scalar.shape[0]))
+            return node_scalar + res_s, node_vector + res_v
         filter_out = fw * gather(self.scalar_message_mlp(node_scalar), src)
         gate_v, gate_e, msg_s = torch.split(filter_out, self.node_size, dim=1)
 
@@ -77,12 +98,12 @@ class _PNAEqConv(nn.Module):
         self.update = PainnUpdate(size)
 
     def forward(self, inv_node_feat, equiv_node_feat, edge_index,
-                edge_diff, edge_dist, vec_state, **kwargs):
+                edge_diff, edge_dist, vec_state, plans=None, **kwargs):
         s = inv_node_feat
         v = vec_state.get("v")
         if v is None or v.shape[-1] != self.size:
             v = s.new_zeros(s.shape[0], 3, self.size)
-        s, v = self.message(s, v, edge_index, edge_diff, edge_dist)
+        s, v = self.message(s, v, edge_index, edge_diff, edge_dist, plans)
         s, v = self.update(s, v)
         vec_state["v"] = v
         return s, equiv_node_feat
@@ -116,12 +137,17 @@ class PNAEqStack(Base):
         if not torch.is_floating_point(x):
             x = x.float()
         x = self.node_embed(x.to(self.node_embed.weight.dtype))
-        return x, data.pos, {
+        conv_args = {
             "edge_index": data.edge_index,
             "edge_diff": edge_diff,
             "edge_dist": edge_dist,
             "vec_state": {},
         }
+        if fused_painn(FUSED_BY_DEFAULT):
+            conv_args["plans"] = message_plans(
+                data.edge_index, x.shape[0],
+                getattr(self, "_edges_sorted", False))
+        return x, data.pos, conv_args
 
     def __str__(self):
         return "PNAEqStack"

@@ -777,6 +777,21 @@ torch::Tensor gather_mul(torch::Tensor a, torch::Tensor b,
                          c10::optional<torch::Tensor> ia,
                          c10::optional<torch::Tensor> ib, long E);
 
+// defined in painn_message.hip
+std::vector<torch::Tensor> painn_msg_fwd(
+    torch::Tensor phi, torch::Tensor w, torch::Tensor v, torch::Tensor u,
+    torch::Tensor sidx, torch::Tensor rowptr,
+    c10::optional<torch::Tensor> perm, bool scalar);
+std::vector<torch::Tensor> painn_msg_bwd_node(
+    torch::Tensor phi, torch::Tensor w, torch::Tensor v, torch::Tensor u,
+    c10::optional<torch::Tensor> gs, torch::Tensor gv, torch::Tensor didx,
+    torch::Tensor rowptr, c10::optional<torch::Tensor> perm, bool need_phi,
+    bool need_v);
+std::vector<torch::Tensor> painn_msg_bwd_edge(
+    torch::Tensor phi, torch::Tensor w, torch::Tensor v, torch::Tensor u,
+    c10::optional<torch::Tensor> gs, torch::Tensor gv, torch::Tensor sidx,
+    torch::Tensor didx, bool need_w, bool need_u);
+
 // defined in act_linear.hip
 torch::Tensor act_linear_fwd(torch::Tensor h, torch::Tensor W,
                              c10::optional<torch::Tensor> bias);
@@ -824,6 +839,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "identity",
         pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("ia"),
         pybind11::arg("ib"), pybind11::arg("E"));
+  m.def("painn_msg_fwd", &painn_msg_fwd,
+        "fused PaiNN message -> (ds | None, dv) over the CSR rows of the "
+        "destinations (HIP)",
+        pybind11::arg("phi"), pybind11::arg("w"), pybind11::arg("v"),
+        pybind11::arg("u"), pybind11::arg("sidx"), pybind11::arg("rowptr"),
+        pybind11::arg("perm"), pybind11::arg("scalar"));
+  m.def("painn_msg_bwd_node", &painn_msg_bwd_node,
+        "fused PaiNN message backward -> (dphi | None, dv_in | None) over "
+        "the CSR rows of the sources (HIP)",
+        pybind11::arg("phi"), pybind11::arg("w"), pybind11::arg("v"),
+        pybind11::arg("u"), pybind11::arg("gs"), pybind11::arg("gv"),
+        pybind11::arg("didx"), pybind11::arg("rowptr"),
+        pybind11::arg("perm"), pybind11::arg("need_phi"),
+        pybind11::arg("need_v"));
+  m.def("painn_msg_bwd_edge", &painn_msg_bwd_edge,
+        "fused PaiNN message backward -> (dw | None, du | None), per edge "
+        "(HIP)",
+        pybind11::arg("phi"), pybind11::arg("w"), pybind11::arg("v"),
+        pybind11::arg("u"), pybind11::arg("gs"), pybind11::arg("gv"),
+        pybind11::arg("sidx"), pybind11::arg("didx"),
+        pybind11::arg("need_w"), pybind11::arg("need_u"));
   m.def("pna_fwd", &pna_fwd,
         "fused PNA aggregation -> (out, stats, arg) (HIP); aggregator "
         "ids: 0 sum, 1 mean, 2 min, 3 max, 4 std, 5 var",

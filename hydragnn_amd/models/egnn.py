@@ -13,11 +13,28 @@ from typing import Optional
 
 import torch
 from torch import nn
+from torch.nn import functional as F
 
-from ..ops.mfma_linear import MFMALinear
+from ..ops import act_linear as al
+from ..ops.edge_affine import MAX_EDGE_DIM, edge_pair_affine, fused_egnn
+from ..ops.gather_mul import SegmentPlan
+from ..ops.mfma_linear import (MFMALinear, _bf16_ok, _eligible,
+                               mfma_linear_bf16)
+from ..ops._extension import use_eager
 
 from ..ops import gather, get_edge_vectors_and_lengths, scatter
 from .base import Base
+
+# HYDRAGNN_EGNN_FUSED unset: see profiles/README.md for the measurement
+FUSED_BY_DEFAULT = False
+
+
+def message_plans(edge_index, num_nodes, edges_sorted):
+    """The (src, dst) SegmentPlans of one batch's edges over its nodes,
+    shared by every layer of a stack."""
+    return (SegmentPlan.from_index(edge_index[0], num_nodes),
+            SegmentPlan.from_index(edge_index[1], num_nodes,
+                                   sorted_index=edges_sorted))
 
 
 class E_GCL(nn.Module):
@@ -39,17 +56,59 @@ class E_GCL(nn.Module):
             self.coord_mlp = nn.Sequential(
                 MFMALinear(hidden_nf, hidden_nf), act, layer)
 
-    def forward(self, h, pos, edge_index, edge_attr=None, edge_shifts=None):
+    def _fused_edge_mlp(self, h, r2, edge_attr, edge_index, plans):
+        """edge_mlp without the concatenation: the first layer splits by
+        the blocks [W_i | W_j | w_r | W_e] of its weight into a node-side
+        GEMM and `edge_pair_affine`; the second consumes the
+        pre-activation on the fused SiLU GEMMs where they apply."""
+        lin1, act, lin2 = self.edge_mlp[0], self.edge_mlp[1], self.edge_mlp[2]
+        n, feat = h.shape
+        if plans is None:
+            plans = message_plans(edge_index, n,
+                                  getattr(self, "_edges_sorted", False))
+        hip_ok = h.is_cuda and not use_eager() and _bf16_ok(h)
+        W = lin1.weight
+        W_ij = torch.cat([W[:, :feat], W[:, feat:2 * feat]], dim=0)
+        if hip_ok and _eligible(n, W_ij.shape[0], feat):
+            P = mfma_linear_bf16(h, W_ij, None)
+        else:
+            P = F.linear(h, W_ij if torch.is_autocast_enabled()
+                         else W_ij.to(h.dtype))
+        # the parameter casts are differentiable ops out here, so second
+        # order terms reach the fp32 leaves
+        dt = P.dtype
+        z = edge_pair_affine(
+            P, r2.to(dt), None if edge_attr is None else edge_attr.to(dt),
+            W[:, 2 * feat].to(dt),
+            None if edge_attr is None else W[:, 2 * feat + 1:].to(dt),
+            None if lin1.bias is None else lin1.bias.to(dt),
+            plans[0], plans[1])
+        hidden = lin2.out_features
+        if (isinstance(act, nn.SiLU) and al.fused_route()
+                and z.is_cuda and z.dtype == torch.bfloat16
+                and not use_eager()
+                and al.in_envelope(z.shape[0], hidden, hidden)):
+            bias = lin2.bias
+            return self.edge_mlp[3](al.act_linear(
+                z, lin2.weight.to(dt), None if bias is None else bias.to(dt)))
+        return self.edge_mlp[3](lin2(act(z)))
+
+    def forward(self, h, pos, edge_index, edge_attr=None, edge_shifts=None,
+                plans=None):
         src, dst = edge_index[0], edge_index[1]
         vec, lengths = get_edge_vectors_and_lengths(pos, edge_index,
                                                     edge_shifts)
         r2 = (lengths ** 2)
-        hi = gather(h, dst)
-        hj = gather(h, src)
-        parts = [hi, hj, r2.to(h.dtype)]
-        if edge_attr is not None:
-            parts.append(edge_attr)
-        m = self.edge_mlp(torch.cat(parts, dim=-1))
+        edge_dim = 0 if edge_attr is None else edge_attr.shape[-1]
+        if fused_egnn(FUSED_BY_DEFAULT) and edge_dim <= MAX_EDGE_DIM:
+            m = self._fused_edge_mlp(h, r2, edge_attr, edge_index, plans)
+        else:
+            hi = gather(h, dst)
+            hj = gather(h, src)
+            parts = [hi, hj, r2.to(h.dtype)]
+            if edge_attr is not None:
+                parts.append(edge_attr)
+            m = self.edge_mlp(torch.cat(parts, dim=-1))
         if self.equivariant:
             trans = vec.to(h.dtype) * self.coord_mlp(m)
             pos = pos + scatter(
@@ -68,9 +127,10 @@ class _EGCLWrapper(nn.Module):
         self.conv = conv
 
     def forward(self, inv_node_feat, equiv_node_feat, edge_index,
-                edge_attr=None, edge_shifts=None, **kwargs):
+                edge_attr=None, edge_shifts=None, plans=None, **kwargs):
         h, pos = self.conv(inv_node_feat, equiv_node_feat, edge_index,
-                           edge_attr=edge_attr, edge_shifts=edge_shifts)
+                           edge_attr=edge_attr, edge_shifts=edge_shifts,
+                           plans=plans)
         return h, pos
 
 
@@ -100,6 +160,10 @@ class EGCLStack(Base):
             x = x.float()
         if self.use_global_attn and not self.is_equivariant_attn:
             x, conv_args = self._gps_encode(data, x, conv_args)
+        if fused_egnn(FUSED_BY_DEFAULT):
+            conv_args["plans"] = message_plans(
+                data.edge_index, data.pos.shape[0],
+                getattr(self, "_edges_sorted", False))
         return x, data.pos, conv_args
 
     def __str__(self):

@@ -29,6 +29,8 @@ from .pna_aggr import (pna_aggregate, pna_scale, path_counts,
                        reset_path_counts)
 from .gather_mul import SegmentPlan, gather_mul_sum, gather_mul
 from .painn_message import painn_message
+from .edge_affine import (edge_pair_affine, pair_affine_node,
+                          pair_affine_edge, pair_affine_param)
 from .mfma_linear import MFMALinear
 from .splitk_linear import SplitKLinear
 
@@ -43,4 +45,6 @@ __all__ = [
     "segment_outer_sum", "segment_matvec",
     "pna_aggregate", "pna_scale", "path_counts", "reset_path_counts",
     "SegmentPlan", "gather_mul_sum", "gather_mul", "painn_message",
+    "edge_pair_affine", "pair_affine_node", "pair_affine_edge",
+    "pair_affine_param",
 ]

@@ -792,6 +792,25 @@ std::vector<torch::Tensor> painn_msg_bwd_edge(
     c10::optional<torch::Tensor> gs, torch::Tensor gv, torch::Tensor sidx,
     torch::Tensor didx, bool need_w, bool need_u);
 
+// defined in edge_affine.hip
+torch::Tensor pair_affine_fwd(
+    c10::optional<torch::Tensor> P, c10::optional<torch::Tensor> r2,
+    c10::optional<torch::Tensor> ea, c10::optional<torch::Tensor> wr,
+    c10::optional<torch::Tensor> weT, c10::optional<torch::Tensor> b,
+    c10::optional<torch::Tensor> didx, c10::optional<torch::Tensor> sidx,
+    long E, long H, torch::Tensor like);
+torch::Tensor pair_affine_node(torch::Tensor g, torch::Tensor d_rowptr,
+                               c10::optional<torch::Tensor> d_perm,
+                               torch::Tensor s_rowptr,
+                               c10::optional<torch::Tensor> s_perm, long N);
+std::vector<torch::Tensor> pair_affine_edge(
+    torch::Tensor g, c10::optional<torch::Tensor> wr,
+    c10::optional<torch::Tensor> weT);
+std::vector<torch::Tensor> pair_affine_param(
+    torch::Tensor g, c10::optional<torch::Tensor> r2,
+    c10::optional<torch::Tensor> ea, bool want_bias);
+long pair_affine_param_chunks(long E);
+
 // defined in act_linear.hip
 torch::Tensor act_linear_fwd(torch::Tensor h, torch::Tensor W,
                              c10::optional<torch::Tensor> bias);
@@ -829,6 +848,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("act") = true, pybind11::arg("want_bias") = false);
   m.def("act_linear_wgrad_chunks", &act_linear_wgrad_chunks,
         "E-chunks of an act_linear_wgrad launch: a function of E alone");
+  m.def("pair_affine_fwd", &pair_affine_fwd,
+        "z[e] = P[dst e, :H] + P[src e, H:] + r2[e] w_r + W_e ea[e] + b, "
+        "every group optional (HIP)",
+        pybind11::arg("P"), pybind11::arg("r2"), pybind11::arg("ea"),
+        pybind11::arg("wr"), pybind11::arg("weT"), pybind11::arg("b"),
+        pybind11::arg("didx"), pybind11::arg("sidx"), pybind11::arg("E"),
+        pybind11::arg("H"), pybind11::arg("like"));
+  m.def("pair_affine_node", &pair_affine_node,
+        "dP[N, 2H]: g summed over the dst rows | over the src rows (HIP)",
+        pybind11::arg("g"), pybind11::arg("d_rowptr"),
+        pybind11::arg("d_perm"), pybind11::arg("s_rowptr"),
+        pybind11::arg("s_perm"), pybind11::arg("N"));
+  m.def("pair_affine_edge", &pair_affine_edge,
+        "(dr2 | None, dea | None) = (g w_r, g W_e) per edge (HIP)",
+        pybind11::arg("g"), pybind11::arg("wr"), pybind11::arg("weT"));
+  m.def("pair_affine_param", &pair_affine_param,
+        "(dw_r | None, dW_e | None, db | None): sums over the edges of "
+        "r2 g, ea g and g (HIP)",
+        pybind11::arg("g"), pybind11::arg("r2"), pybind11::arg("ea"),
+        pybind11::arg("want_bias"));
+  m.def("pair_affine_param_chunks", &pair_affine_param_chunks,
+        "E-chunks of a pair_affine_param launch: a function of E alone");
   m.def("gather_mul_sum", &gather_mul_sum,
         "out[i] = sum over CSR row i of x[gidx[e]] * w[e] (HIP); an "
         "absent gidx is the identity",

@@ -23,6 +23,7 @@ ext_modules = [
                  "hydragnn_amd/ops/csrc/pna_aggr.hip",
                  "hydragnn_amd/ops/csrc/gather_mul.hip",
                  "hydragnn_amd/ops/csrc/painn_message.hip",
+                 "hydragnn_amd/ops/csrc/edge_affine.hip",
                  "hydragnn_amd/ops/csrc/act_linear.hip"],
         extra_compile_args={
             "cxx": ["-O3"],

@@ -328,15 +328,15 @@ class DIMEStack(Base):
             # triplets(), idx_kj does not), the edge -> node groupings
             # and the identity over the edges
             n_edges = ei.shape[1]
+            src, dst = SegmentPlan.pair(
+                ei, data.num_nodes, getattr(self, "_edges_sorted", False))
             plans = {
                 "kj": SegmentPlan.from_index(idx_kj, n_edges),
                 "ji": SegmentPlan.from_index(idx_ji, n_edges,
                                              sorted_index=True),
                 "edge": SegmentPlan.identity(n_edges, ei.device),
-                "src": SegmentPlan.from_index(ei[0], data.num_nodes),
-                "dst": SegmentPlan.from_index(
-                    ei[1], data.num_nodes,
-                    sorted_index=getattr(self, "_edges_sorted", False)),
+                "src": src,
+                "dst": dst,
             }
         m = self.emb_block(x, rbf, ei, plans)
         conv_args = {

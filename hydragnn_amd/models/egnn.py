@@ -17,7 +17,7 @@ from torch.nn import functional as F
 
 from ..ops import act_linear as al
 from ..ops.edge_affine import MAX_EDGE_DIM, edge_pair_affine, fused_egnn
-from ..ops.gather_mul import SegmentPlan
+from ..ops.segment_plan import SegmentPlan
 from ..ops.mfma_linear import (MFMALinear, _bf16_ok, _eligible,
                                mfma_linear_bf16)
 from ..ops._extension import use_eager
@@ -27,14 +27,6 @@ from .base import Base
 
 # HYDRAGNN_EGNN_FUSED unset: see profiles/README.md for the measurement
 FUSED_BY_DEFAULT = False
-
-
-def message_plans(edge_index, num_nodes, edges_sorted):
-    """The (src, dst) SegmentPlans of one batch's edges over its nodes,
-    shared by every layer of a stack."""
-    return (SegmentPlan.from_index(edge_index[0], num_nodes),
-            SegmentPlan.from_index(edge_index[1], num_nodes,
-                                   sorted_index=edges_sorted))
 
 
 class E_GCL(nn.Module):
@@ -64,8 +56,8 @@ class E_GCL(nn.Module):
         lin1, act, lin2 = self.edge_mlp[0], self.edge_mlp[1], self.edge_mlp[2]
         n, feat = h.shape
         if plans is None:
-            plans = message_plans(edge_index, n,
-                                  getattr(self, "_edges_sorted", False))
+            plans = SegmentPlan.pair(edge_index, n,
+                                     getattr(self, "_edges_sorted", False))
         hip_ok = h.is_cuda and not use_eager() and _bf16_ok(h)
         W = lin1.weight
         W_ij = torch.cat([W[:, :feat], W[:, feat:2 * feat]], dim=0)
@@ -161,7 +153,7 @@ class EGCLStack(Base):
         if self.use_global_attn and not self.is_equivariant_attn:
             x, conv_args = self._gps_encode(data, x, conv_args)
         if fused_egnn(FUSED_BY_DEFAULT):
-            conv_args["plans"] = message_plans(
+            conv_args["plans"] = SegmentPlan.pair(
                 data.edge_index, data.pos.shape[0],
                 getattr(self, "_edges_sorted", False))
         return x, data.pos, conv_args

@@ -191,11 +191,9 @@ class DegreeScalerAggregation(nn.Module):
     def _fused(self, msg) -> bool:
         """Device tensors of the kernel dtypes with known aggregators
         and scalers take the fused op, unless HYDRAGNN_PNA_FUSED=0."""
-        import os
         return (msg.is_cuda and msg.dim() == 2
-                and msg.dtype in (torch.float32, torch.float64,
-                                  torch.bfloat16, torch.float16)
-                and os.environ.get("HYDRAGNN_PNA_FUSED", "1") != "0"
+                and msg.dtype in pna_aggr.KERNEL_DTYPES
+                and pna_aggr.fused_pna()
                 and len(set(self.aggregators)) == len(self.aggregators)
                 and all(a in pna_aggr.AGGREGATORS
                         for a in self.aggregators)

@@ -21,7 +21,7 @@ from ..ops import (
     scatter,
     sinc_basis,
 )
-from ..ops.gather_mul import SegmentPlan
+from ..ops.segment_plan import SegmentPlan
 from ..ops.mfma_linear import MFMALinear
 from ..ops.painn_message import fused_painn, painn_message
 from .base import Base
@@ -38,14 +38,6 @@ def common_dtype(*tensors):
     for t in tensors[1:]:
         dt = torch.promote_types(dt, t.dtype)
     return [t.to(dt) for t in tensors]
-
-
-def message_plans(edge_index, num_nodes, edges_sorted):
-    """The (src, dst) SegmentPlans of one batch's edges over its nodes,
-    shared by every layer of a stack."""
-    return (SegmentPlan.from_index(edge_index[0], num_nodes),
-            SegmentPlan.from_index(edge_index[1], num_nodes,
-                                   sorted_index=edges_sorted))
 
 
 class PainnMessage(nn.Module):
@@ -204,7 +196,7 @@ class PAINNStack(Base):
             "vec_state": {},
         }
         if fused_painn(FUSED_BY_DEFAULT):
-            conv_args["plans"] = message_plans(
+            conv_args["plans"] = SegmentPlan.pair(
                 data.edge_index, x.shape[0],
                 getattr(self, "_edges_sorted", False))
         if self.use_global_attn:

@@ -22,9 +22,10 @@ from ..ops import (
 )
 from ..ops.mfma_linear import MFMALinear
 from ..ops.painn_message import fused_painn, painn_message
+from ..ops.segment_plan import SegmentPlan
 from .base import Base, BatchNormNode
 from .layers import DegreeScalerAggregation
-from .painn import PainnUpdate, common_dtype, message_plans
+from .painn import PainnUpdate, common_dtype
 
 # the unset default of HYDRAGNN_PAINN_FUSED for this stack, from the
 # end-to-end step (profiles/README.md)
@@ -144,7 +145,7 @@ class PNAEqStack(Base):
             "vec_state": {},
         }
         if fused_painn(FUSED_BY_DEFAULT):
-            conv_args["plans"] = message_plans(
+            conv_args["plans"] = SegmentPlan.pair(
                 data.edge_index, x.shape[0],
                 getattr(self, "_edges_sorted", False))
         return x, data.pos, conv_args

@@ -119,10 +119,8 @@ class _SCFWrapper(nn.Module):
         per batch."""
         if cache is not None and "plans" in cache:
             return cache["plans"]
-        plans = (SegmentPlan.from_index(edge_index[0], num_nodes),
-                 SegmentPlan.from_index(
-                     edge_index[1], num_nodes,
-                     sorted_index=getattr(self, "_edges_sorted", False)))
+        plans = SegmentPlan.pair(edge_index, num_nodes,
+                                 getattr(self, "_edges_sorted", False))
         if cache is not None:
             cache["plans"] = plans
         return plans

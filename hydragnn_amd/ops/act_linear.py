@@ -40,6 +40,7 @@ import os
 import torch
 
 from ._extension import get_extension, use_eager
+from .segment_plan import acc_dtype
 
 __all__ = ["act_linear", "fused_route", "in_envelope", "path_counts",
            "reset_path_counts"]
@@ -73,11 +74,6 @@ def in_envelope(E: int, N: int, K: int) -> bool:
             and 64 <= K <= 256 and E >= 256)
 
 
-def _acc(dtype: torch.dtype) -> torch.dtype:
-    return torch.float32 if dtype in (torch.bfloat16, torch.float16) \
-        else dtype
-
-
 # ---------------------------------------------------------------------------
 # pure-torch doubles (differentiable)
 # ---------------------------------------------------------------------------
@@ -96,7 +92,7 @@ def _d2phi(x):
 
 
 def torch_act_linear(h, W, b=None):
-    acc = _acc(h.dtype)
+    acc = acc_dtype(h.dtype)
     p = _phi(h.to(acc)).to(h.dtype)
     y = p.to(acc) @ W.to(acc).t()
     if b is not None:
@@ -105,12 +101,12 @@ def torch_act_linear(h, W, b=None):
 
 
 def torch_dgrad(g, W, h):
-    acc = _acc(h.dtype)
+    acc = acc_dtype(h.dtype)
     return ((g.to(acc) @ W.to(acc)) * _dphi(h.to(acc))).to(h.dtype)
 
 
 def torch_wgrad(g, h, u=None, want_bias=False, act=True):
-    acc = _acc(h.dtype)
+    acc = acc_dtype(h.dtype)
     p = h.to(acc)
     if u is not None:
         p = u.to(acc) * _dphi(p)
@@ -122,13 +118,13 @@ def torch_wgrad(g, h, u=None, want_bias=False, act=True):
 
 
 def torch_dgrad_dg(u, W, h):
-    acc = _acc(h.dtype)
+    acc = acc_dtype(h.dtype)
     p = (u.to(acc) * _dphi(h.to(acc))).to(h.dtype)
     return (p.to(acc) @ W.to(acc).t()).to(h.dtype)
 
 
 def torch_dgrad_dh(u, g, W, h):
-    acc = _acc(h.dtype)
+    acc = acc_dtype(h.dtype)
     return (u.to(acc) * (g.to(acc) @ W.to(acc))
             * _d2phi(h.to(acc))).to(h.dtype)
 

@@ -52,84 +52,16 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
-#include "check_launch.h"
+#include "segment_common.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kGridCap = 8192;
+using namespace segment;
+
 constexpr int kMaxD = 16;
 constexpr int kAhead = 4;        // node: positions loaded ahead of the adds
 constexpr int kMaxChunks = 512;  // param: chunks of E
 constexpr int kChunkUnit = 256;  // param: fewest edges worth a chunk
-
-template <int BYTES> struct UIntOf;
-template <> struct UIntOf<2> { using type = unsigned short; };
-template <> struct UIntOf<4> { using type = unsigned int; };
-template <> struct UIntOf<8> { using type = unsigned long; };
-
-// A pack holds the bit patterns of its elements, and elements go to and
-// from the accumulator type without an object of T in between, so that
-// the operand arrays stay in registers (see painn_message.hip).
-template <typename T, int VEC>
-struct alignas(sizeof(T) * VEC) Pack {
-  typename UIntOf<sizeof(T)>::type v[VEC];
-};
-
-template <typename T> struct Bits;
-template <> struct Bits<float> {
-  static __device__ __forceinline__ float get(unsigned int b) {
-    return __uint_as_float(b);
-  }
-  static __device__ __forceinline__ unsigned int put(float x) {
-    return __float_as_uint(x);
-  }
-};
-template <> struct Bits<double> {
-  static __device__ __forceinline__ double get(unsigned long b) {
-    return __longlong_as_double((long long)b);
-  }
-  static __device__ __forceinline__ unsigned long put(double x) {
-    return (unsigned long)__double_as_longlong(x);
-  }
-};
-template <> struct Bits<c10::BFloat16> {
-  static __device__ __forceinline__ float get(unsigned short b) {
-    return __uint_as_float((unsigned int)b << 16);
-  }
-  static __device__ __forceinline__ unsigned short put(float x) {
-    return c10::detail::round_to_nearest_even(x);
-  }
-};
-template <> struct Bits<c10::Half> {
-  static __device__ __forceinline__ float get(unsigned short b) {
-    return __half2float(__ushort_as_half(b));
-  }
-  static __device__ __forceinline__ unsigned short put(float x) {
-    return __half_as_ushort(__float2half(x));
-  }
-};
-
-template <typename ACC, typename T, int VEC>
-__device__ __forceinline__ ACC ld(const Pack<T, VEC>& p, int k) {
-  return Bits<T>::get(p.v[k]);
-}
-
-template <typename T, int VEC, typename ACC>
-__device__ __forceinline__ void st(Pack<T, VEC>& p, int k, ACC x) {
-  p.v[k] = Bits<T>::put(x);
-}
-
-// element i of a plain array of T
-template <typename ACC, typename T>
-__device__ __forceinline__ ACC ld1(const T* __restrict__ a, long i) {
-  return ld<ACC>(reinterpret_cast<const Pack<T, 1>*>(a)[i], 0);
-}
-
-template <typename T, typename ACC>
-__device__ __forceinline__ void st1(T* __restrict__ a, long i, ACC x) {
-  st(reinterpret_cast<Pack<T, 1>*>(a)[i], 0, x);
-}
 
 // no fused multiply-add anywhere below: a product is rounded, then added
 #pragma clang fp contract(off)
@@ -141,9 +73,6 @@ __device__ __forceinline__ void st1(T* __restrict__ a, long i, ACC x) {
 #pragma clang attribute push( \
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
-
-__device__ inline float mul_rn(float a, float b) { return __fmul_rn(a, b); }
-__device__ inline double mul_rn(double a, double b) { return __dmul_rn(a, b); }
 
 // The block's tile of r2 (n rows from row0) and ea (n rows of D) into
 // LDS, coalesced; rows past E read as 0.  Either source may be null.
@@ -451,22 +380,6 @@ __global__ void __launch_bounds__(kBlock) pair_affine_param_reduce_kernel(
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-inline int n_blocks(long threads) {
-  long b = (threads + kBlock - 1) / kBlock;
-  return (int)std::min<long>(std::max<long>(b, 1), kGridCap);
-}
-
-inline bool aligned16(const void* p) {
-  return reinterpret_cast<uintptr_t>(p) % 16 == 0;
-}
-
-// the least power of two >= n, at most cap
-inline int pow2_at_least(long n, int cap) {
-  int L = 1;
-  while (L < cap && L < n) L <<= 1;
-  return L;
-}
-
 using OptTensor = c10::optional<torch::Tensor>;
 
 // a null pointer for an absent operand; a present one must be a
@@ -479,16 +392,6 @@ const void* operand(const OptTensor& t, at::ScalarType dtype, long numel,
               "pair_affine: ", what, " must be a contiguous GPU tensor of ",
               numel, " elements of the common dtype");
   return t->data_ptr();
-}
-
-const long* index_ptr(const OptTensor& idx, long n, const char* what) {
-  if (!idx.has_value()) return nullptr;
-  TORCH_CHECK(idx->is_cuda() && idx->dtype() == torch::kLong &&
-                  idx->is_contiguous() && idx->dim() == 1 &&
-                  idx->numel() == n,
-              "pair_affine: ", what, " must be contiguous int64 [", n,
-              "] on the device");
-  return idx->data_ptr<long>();
 }
 
 void check_sizes(long E, long H, long D) {
@@ -527,8 +430,11 @@ torch::Tensor pair_affine_fwd(OptTensor P, OptTensor r2, OptTensor ea,
   const void* wv = operand(wr, dtype, H, "w_r");
   const void* tv = operand(weT, dtype, D * H, "W_e^T");
   const void* bv = operand(b, dtype, H, "b");
-  const long* dp = P.has_value() ? index_ptr(didx, E, "dst") : nullptr;
-  const long* sp = P.has_value() ? index_ptr(sidx, E, "src") : nullptr;
+  torch::Tensor dk, sk;
+  const long* dp =
+      P.has_value() ? index_ptr(didx, E, dk, "pair_affine: dst") : nullptr;
+  const long* sp =
+      P.has_value() ? index_ptr(sidx, E, sk, "pair_affine: src") : nullptr;
   if (E * H == 0 || (P.has_value() && N == 0) ||
       !(Pv || rv || (ev && D > 0) || bv))
     return torch::zeros({E, H}, like.options());
@@ -541,9 +447,8 @@ torch::Tensor pair_affine_fwd(OptTensor P, OptTensor r2, OptTensor ea,
         using acc_t = at::opmath_type<scalar_t>;
         constexpr int kVec = 16 / sizeof(scalar_t);
         scalar_t* zp = z.data_ptr<scalar_t>();
-        const bool packed = H % kVec == 0 && aligned16(Pv) &&
-                            aligned16(wv) && aligned16(tv) && aligned16(bv) &&
-                            aligned16(zp);
+        const bool packed =
+            H % kVec == 0 && all_aligned16(Pv, wv, tv, bv, zp);
         auto launch = [&](auto kernel, long Fp) {
           const int L = pow2_at_least(Fp, 64);
           const int G = kBlock / L;
@@ -580,10 +485,11 @@ torch::Tensor pair_affine_node(torch::Tensor g, torch::Tensor d_rowptr,
   const long E = g.size(0), H = g.size(1);
   check_sizes(E, H, 0);
   TORCH_CHECK(N >= 0, "pair_affine_node: N must not be negative");
-  const long* drp = index_ptr(d_rowptr, N + 1, "the dst rowptr");
-  const long* srp = index_ptr(s_rowptr, N + 1, "the src rowptr");
-  const long* dpp = index_ptr(d_perm, E, "the dst perm");
-  const long* spp = index_ptr(s_perm, E, "the src perm");
+  torch::Tensor drk, srk, dpk, spk;
+  const long* drp = rowptr_ptr(d_rowptr, N, drk);
+  const long* srp = rowptr_ptr(s_rowptr, N, srk);
+  const long* dpp = index_ptr(d_perm, E, dpk, "pair_affine: the dst perm");
+  const long* spp = index_ptr(s_perm, E, spk, "pair_affine: the src perm");
   if (N * H == 0 || E == 0) return torch::zeros({N, 2 * H}, g.options());
   auto dP = torch::empty({N, 2 * H}, g.options());
   auto stream = at::hip::getCurrentHIPStream().stream();
@@ -598,7 +504,7 @@ torch::Tensor pair_affine_node(torch::Tensor g, torch::Tensor d_rowptr,
           hipLaunchKernelGGL(kernel, dim3(n_blocks(N * 2 * Fp)), dim3(kBlock),
                              0, stream, gp, drp, dpp, srp, spp, op, N, Fp);
         };
-        if (H % kVec == 0 && aligned16(gp) && aligned16(op))
+        if (H % kVec == 0 && all_aligned16(gp, op))
           launch(pair_affine_node_kernel<scalar_t, acc_t, kVec>, H / kVec);
         else
           launch(pair_affine_node_kernel<scalar_t, acc_t, 1>, H);
@@ -636,8 +542,7 @@ std::vector<torch::Tensor> pair_affine_edge(torch::Tensor g, OptTensor wr,
         const scalar_t* gp = g.data_ptr<scalar_t>();
         scalar_t* o_r = wr.has_value() ? dr2.data_ptr<scalar_t>() : nullptr;
         scalar_t* o_e = D > 0 ? dea.data_ptr<scalar_t>() : nullptr;
-        const bool packed = H % kVec == 0 && aligned16(gp) &&
-                            aligned16(wv) && aligned16(tv);
+        const bool packed = H % kVec == 0 && all_aligned16(gp, wv, tv);
         auto launch = [&](auto kernel, long Fp) {
           const int L = pow2_at_least(Fp, 64);
           hipLaunchKernelGGL(kernel, dim3(n_blocks(E * L)), dim3(kBlock), 0,

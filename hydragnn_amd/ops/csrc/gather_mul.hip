@@ -32,26 +32,16 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
-#include "check_launch.h"
+#include "segment_common.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kGridCap = 8192;
+using namespace segment;
+
 constexpr int kUnroll = 4;      // positions of a row loaded ahead of the adds
 
-template <typename T, int VEC>
-struct alignas(sizeof(T) * VEC) Pack {
-  T v[VEC];
-};
-
-// __fmul_rn / __dmul_rn are a plain product in the HIP headers, which
-// the compiler's default (contract = fast) still fuses with the add
-// that follows; this turns contraction off for the rest of the file.
+// no fused multiply-add anywhere below: a product is rounded, then added
 #pragma clang fp contract(off)
-
-__device__ inline float mul_rn(float a, float b) { return __fmul_rn(a, b); }
-__device__ inline double mul_rn(double a, double b) { return __dmul_rn(a, b); }
 
 template <typename T, typename ACC, int VEC>
 __global__ void gms_kernel(const T* __restrict__ x, const T* __restrict__ w,
@@ -89,7 +79,7 @@ __global__ void gms_kernel(const T* __restrict__ x, const T* __restrict__ w,
       for (int u = 0; u < kUnroll; ++u)
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
-          acc[k] += mul_rn((ACC)xv[u].v[k], (ACC)wv[u].v[k]);
+          acc[k] += mul_rn(ld<ACC>(xv[u], k), ld<ACC>(wv[u], k));
     }
     for (; p < hi; ++p) {
       const long e = perm ? perm[p] : p;
@@ -98,11 +88,11 @@ __global__ void gms_kernel(const T* __restrict__ x, const T* __restrict__ w,
       const P wv = wp[e * Fp + f];
 #pragma unroll
       for (int k = 0; k < VEC; ++k)
-        acc[k] += mul_rn((ACC)xv.v[k], (ACC)wv.v[k]);
+        acc[k] += mul_rn(ld<ACC>(xv, k), ld<ACC>(wv, k));
     }
     P o;
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) o.v[k] = (T)acc[k];
+    for (int k = 0; k < VEC; ++k) st(o, k, acc[k]);
     op[i] = o;
   }
 }
@@ -129,18 +119,9 @@ __global__ void gm_kernel(const T* __restrict__ a, const T* __restrict__ b,
     P o;
 #pragma unroll
     for (int k = 0; k < VEC; ++k)
-      o.v[k] = (T)mul_rn((ACC)av.v[k], (ACC)bv.v[k]);
+      st(o, k, mul_rn(ld<ACC>(av, k), ld<ACC>(bv, k)));
     op[i] = o;
   }
-}
-
-inline int n_blocks(long total) {
-  long b = (total + kBlock - 1) / kBlock;
-  return (int)std::min<long>(b, kGridCap);
-}
-
-inline bool aligned16(const void* p) {
-  return reinterpret_cast<uintptr_t>(p) % 16 == 0;
 }
 
 void check_rows(const torch::Tensor& t, const torch::Tensor& like,
@@ -150,17 +131,6 @@ void check_rows(const torch::Tensor& t, const torch::Tensor& like,
   TORCH_CHECK(t.scalar_type() == like.scalar_type() &&
                   t.size(1) == like.size(1),
               what, ": both operands must have the same dtype and F");
-}
-
-// a null pointer for an absent (identity) index
-const long* index_ptr(const c10::optional<torch::Tensor>& idx, long n,
-                      torch::Tensor& keep, const char* what) {
-  if (!idx.has_value()) return nullptr;
-  TORCH_CHECK(idx->is_cuda() && idx->dtype() == torch::kLong &&
-                  idx->dim() == 1 && idx->numel() == n,
-              what, " must be int64 [E] on the device");
-  keep = idx->contiguous();
-  return keep.data_ptr<long>();
 }
 
 }  // namespace
@@ -173,19 +143,16 @@ torch::Tensor gather_mul_sum(torch::Tensor x, torch::Tensor w,
                              c10::optional<torch::Tensor> perm) {
   check_rows(x, x, "x");
   check_rows(w, x, "w");
-  TORCH_CHECK(rowptr.is_cuda() && rowptr.dtype() == torch::kLong &&
-                  rowptr.dim() == 1 && rowptr.numel() >= 1,
-              "rowptr must be int64 [N + 1] on the device");
   const long E = w.size(0), N = rowptr.numel() - 1, F = x.size(1);
   TORCH_CHECK(E < (1L << 31), "gather_mul_sum: E must be below 2^31");
   TORCH_CHECK(gidx.has_value() || x.size(0) == E,
               "without a gather index x needs one row per edge");
-  torch::Tensor gk, pk;
+  torch::Tensor gk, pk, rk;
+  const long* rp = rowptr_ptr(rowptr, N, rk);
   const long* gp = index_ptr(gidx, E, gk, "the gather index");
   const long* pp = index_ptr(perm, E, pk, "perm");
   if (N * F == 0 || E == 0) return torch::zeros({N, F}, x.options());
   auto out = torch::empty({N, F}, x.options());
-  auto rp = rowptr.contiguous();
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::BFloat16, at::ScalarType::Half, x.scalar_type(),
       "gather_mul_sum", [&] {
@@ -194,18 +161,17 @@ torch::Tensor gather_mul_sum(torch::Tensor x, torch::Tensor w,
         const scalar_t* xp = x.data_ptr<scalar_t>();
         const scalar_t* wp = w.data_ptr<scalar_t>();
         scalar_t* op = out.data_ptr<scalar_t>();
-        if (F % kVec == 0 && aligned16(xp) && aligned16(wp) &&
-            aligned16(op)) {
+        if (F % kVec == 0 && all_aligned16(xp, wp, op)) {
           const long Fp = F / kVec;
           hipLaunchKernelGGL((gms_kernel<scalar_t, acc_t, kVec>),
                              dim3(n_blocks(N * Fp)), dim3(kBlock), 0,
                              at::hip::getCurrentHIPStream().stream(), xp, wp,
-                             rp.data_ptr<long>(), pp, gp, op, N, Fp);
+                             rp, pp, gp, op, N, Fp);
         } else {
           hipLaunchKernelGGL((gms_kernel<scalar_t, acc_t, 1>),
                              dim3(n_blocks(N * F)), dim3(kBlock), 0,
                              at::hip::getCurrentHIPStream().stream(), xp, wp,
-                             rp.data_ptr<long>(), pp, gp, op, N, F);
+                             rp, pp, gp, op, N, F);
         }
         check_launch("gms_kernel");
       });
@@ -236,8 +202,7 @@ torch::Tensor gather_mul(torch::Tensor a, torch::Tensor b,
         const scalar_t* ap = a.data_ptr<scalar_t>();
         const scalar_t* bp = b.data_ptr<scalar_t>();
         scalar_t* op = out.data_ptr<scalar_t>();
-        if (F % kVec == 0 && aligned16(ap) && aligned16(bp) &&
-            aligned16(op)) {
+        if (F % kVec == 0 && all_aligned16(ap, bp, op)) {
           const long Fp = F / kVec;
           hipLaunchKernelGGL((gm_kernel<scalar_t, kVec>),
                              dim3(n_blocks(E * Fp)), dim3(kBlock), 0,

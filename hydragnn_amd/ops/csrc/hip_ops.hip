@@ -17,9 +17,10 @@
 #include <torch/extension.h>
 #include <ATen/OpMathType.h>
 #include <ATen/hip/HIPContext.h>
-#include <c10/hip/HIPException.h>
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+
+#include "segment_common.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a GPU tensor")
 #define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -27,11 +28,6 @@
 namespace {
 
 constexpr int kBlock = 256;
-
-inline int n_blocks(long total, int block, int cap = 2048) {
-  long b = (total + block - 1) / block;
-  return (int)std::min<long>(b, cap);
-}
 
 // elements of one row: the product of the trailing dims (defined for a
 // tensor of zero rows too)
@@ -41,9 +37,7 @@ inline long row_elems(const torch::Tensor& t) {
   return f;
 }
 
-inline bool aligned16(const void* p) {
-  return reinterpret_cast<uintptr_t>(p) % 16 == 0;
-}
+using segment::aligned16;
 
 // -------------------------------------------------------------------------
 // gather: out[e, f] = src[index[e], f]
@@ -373,9 +367,10 @@ static hipStream_t cur_stream() {
 
 #define LAUNCH(kernel, total, cap, ...)                                   \
   do {                                                                    \
-    hipLaunchKernelGGL(kernel, dim3(n_blocks((total), kBlock, (cap))),    \
+    const long blocks_ = ((total) + kBlock - 1) / kBlock;                 \
+    hipLaunchKernelGGL(kernel, dim3((int)std::min<long>(blocks_, (cap))), \
                        dim3(kBlock), 0, cur_stream(), __VA_ARGS__);       \
-    C10_HIP_KERNEL_LAUNCH_CHECK();                                        \
+    check_launch(#kernel);                                                \
   } while (0)
 
 torch::Tensor gather_fwd(torch::Tensor src, torch::Tensor index) {

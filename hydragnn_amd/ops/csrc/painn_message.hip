@@ -50,79 +50,11 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
-#include "check_launch.h"
+#include "segment_common.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kGridCap = 8192;
-
-template <int BYTES> struct UIntOf;
-template <> struct UIntOf<2> { using type = unsigned short; };
-template <> struct UIntOf<4> { using type = unsigned int; };
-template <> struct UIntOf<8> { using type = unsigned long; };
-
-// A pack holds the bit patterns of its elements, and elements go to and
-// from the accumulator type without an object of T in between: objects
-// of the half class types (their constructors take a generic `this`)
-// would keep the operand arrays in scratch memory instead of registers.
-// The conversions are c10's own: round to nearest even for bf16,
-// __float2half for f16.
-template <typename T, int VEC>
-struct alignas(sizeof(T) * VEC) Pack {
-  typename UIntOf<sizeof(T)>::type v[VEC];
-};
-
-template <typename T> struct Bits;
-template <> struct Bits<float> {
-  static __device__ __forceinline__ float get(unsigned int b) {
-    return __uint_as_float(b);
-  }
-  static __device__ __forceinline__ unsigned int put(float x) {
-    return __float_as_uint(x);
-  }
-};
-template <> struct Bits<double> {
-  static __device__ __forceinline__ double get(unsigned long b) {
-    return __longlong_as_double((long long)b);
-  }
-  static __device__ __forceinline__ unsigned long put(double x) {
-    return (unsigned long)__double_as_longlong(x);
-  }
-};
-template <> struct Bits<c10::BFloat16> {
-  static __device__ __forceinline__ float get(unsigned short b) {
-    return __uint_as_float((unsigned int)b << 16);
-  }
-  static __device__ __forceinline__ unsigned short put(float x) {
-    return c10::detail::round_to_nearest_even(x);
-  }
-};
-template <> struct Bits<c10::Half> {
-  static __device__ __forceinline__ float get(unsigned short b) {
-    return __half2float(__ushort_as_half(b));
-  }
-  static __device__ __forceinline__ unsigned short put(float x) {
-    return __half_as_ushort(__float2half(x));
-  }
-};
-
-// element k of a pack in the accumulator type; a value rounded to T
-template <typename ACC, typename T, int VEC>
-__device__ __forceinline__ ACC ld(const Pack<T, VEC>& p, int k) {
-  return Bits<T>::get(p.v[k]);
-}
-
-template <typename T, int VEC, typename ACC>
-__device__ __forceinline__ void st(Pack<T, VEC>& p, int k, ACC x) {
-  p.v[k] = Bits<T>::put(x);
-}
-
-// element i of a plain array of T
-template <typename ACC, typename T>
-__device__ __forceinline__ ACC ld1(const T* __restrict__ a, long i) {
-  return ld<ACC>(reinterpret_cast<const Pack<T, 1>*>(a)[i], 0);
-}
+using namespace segment;
 
 // positions of a row whose loads are issued ahead of the adds: four for
 // the element-wise instances, two for the 16-byte packs, whose nine
@@ -144,9 +76,6 @@ constexpr int ahead() { return VEC == 1 ? 4 : 2; }
 #pragma clang attribute push( \
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
-
-__device__ inline float mul_rn(float a, float b) { return __fmul_rn(a, b); }
-__device__ inline double mul_rn(double a, double b) { return __dmul_rn(a, b); }
 
 // ---------------------------------------------------------------------------
 // forward
@@ -450,25 +379,6 @@ __global__ void __launch_bounds__(kBlock) painn_msg_bwd_edge_kernel(
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-inline int n_blocks(long threads) {
-  long b = (threads + kBlock - 1) / kBlock;
-  return (int)std::min<long>(b, kGridCap);
-}
-
-inline bool aligned16(const void* p) {
-  return reinterpret_cast<uintptr_t>(p) % 16 == 0;
-}
-
-const long* index_ptr(const c10::optional<torch::Tensor>& idx, long n,
-                      torch::Tensor& keep, const char* what) {
-  if (!idx.has_value()) return nullptr;
-  TORCH_CHECK(idx->is_cuda() && idx->dtype() == torch::kLong &&
-                  idx->dim() == 1 && idx->numel() == n,
-              what, " must be int64 [", n, "] on the device");
-  keep = idx->contiguous();
-  return keep.data_ptr<long>();
-}
-
 struct Shape {
   long N, E, F;
 };
@@ -498,22 +408,6 @@ void check_cotangent(const torch::Tensor& g, const torch::Tensor& like,
                   g.size(0) == rows && g.size(1) == cols,
               what, " must be a contiguous [", rows, ", ", cols,
               "] GPU tensor of the operands' dtype");
-}
-
-const long* rowptr_ptr(const torch::Tensor& rowptr, long N,
-                       torch::Tensor& keep) {
-  TORCH_CHECK(rowptr.is_cuda() && rowptr.dtype() == torch::kLong &&
-                  rowptr.dim() == 1 && rowptr.numel() == N + 1,
-              "rowptr must be int64 [N + 1] on the device");
-  keep = rowptr.contiguous();
-  return keep.data_ptr<long>();
-}
-
-// the least power of two >= packs, at most 64
-inline int lanes_per_edge(long packs) {
-  int L = 1;
-  while (L < 64 && L < packs) L <<= 1;
-  return L;
 }
 
 }  // namespace
@@ -549,9 +443,8 @@ std::vector<torch::Tensor> painn_msg_fwd(
         const scalar_t* d = u.data_ptr<scalar_t>();
         scalar_t* o_s = scalar ? ds.data_ptr<scalar_t>() : nullptr;
         scalar_t* o_v = dv.data_ptr<scalar_t>();
-        const bool packed = s.F % kVec == 0 && aligned16(a) &&
-                            aligned16(b) && aligned16(c) && aligned16(o_s) &&
-                            aligned16(o_v);
+        const bool packed =
+            s.F % kVec == 0 && all_aligned16(a, b, c, o_s, o_v);
         auto launch = [&](auto kernel, long Fp) {
           hipLaunchKernelGGL(kernel, dim3(n_blocks(s.N * Fp)), dim3(kBlock),
                              0, stream, a, b, c, d, rp, pp, sp, o_s, o_v,
@@ -612,10 +505,8 @@ std::vector<torch::Tensor> painn_msg_bwd_node(
         const scalar_t* g_v = gv.data_ptr<scalar_t>();
         scalar_t* o_p = need_phi ? dphi.data_ptr<scalar_t>() : nullptr;
         scalar_t* o_v = need_v ? dvin.data_ptr<scalar_t>() : nullptr;
-        const bool packed = s.F % kVec == 0 && aligned16(a) &&
-                            aligned16(b) && aligned16(c) && aligned16(g_s) &&
-                            aligned16(g_v) && aligned16(o_p) &&
-                            aligned16(o_v);
+        const bool packed =
+            s.F % kVec == 0 && all_aligned16(a, b, c, g_s, g_v, o_p, o_v);
         auto launch = [&](auto kernel, long Fp) {
           hipLaunchKernelGGL(kernel, dim3(n_blocks(s.N * Fp)), dim3(kBlock),
                              0, stream, a, b, c, d, g_s, g_v, rp, pp, dp, o_p,
@@ -668,11 +559,10 @@ std::vector<torch::Tensor> painn_msg_bwd_edge(
         const scalar_t* g_v = gv.data_ptr<scalar_t>();
         scalar_t* o_w = need_w ? dw.data_ptr<scalar_t>() : nullptr;
         scalar_t* o_u = need_u ? du.data_ptr<scalar_t>() : nullptr;
-        const bool packed = s.F % kVec == 0 && aligned16(a) &&
-                            aligned16(b) && aligned16(c) && aligned16(g_s) &&
-                            aligned16(g_v) && aligned16(o_w);
+        const bool packed =
+            s.F % kVec == 0 && all_aligned16(a, b, c, g_s, g_v, o_w);
         auto launch = [&](auto kernel, long Fp) {
-          const int L = lanes_per_edge(Fp);
+          const int L = pow2_at_least(Fp, 64);
           hipLaunchKernelGGL(kernel, dim3(n_blocks(s.E * L)), dim3(kBlock), 0,
                              stream, a, b, c, d, g_s, g_v, sp, dp, o_w, o_u,
                              s.E, Fp, L);

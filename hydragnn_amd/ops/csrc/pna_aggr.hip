@@ -25,15 +25,17 @@
 #include <torch/extension.h>
 #include <ATen/OpMathType.h>
 #include <ATen/hip/HIPContext.h>
-#include <c10/hip/HIPException.h>
 #include <hip/hip_runtime.h>
 
 #include <limits>
 
+#include "segment_common.h"
+
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kGridCap = 8192;
+using segment::kBlock;
+using segment::n_blocks;
+
 constexpr int kMaxAgg = 6;      // sum mean min max std var, each once
 constexpr int kMaxScale = 8;
 
@@ -286,11 +288,6 @@ __global__ void pna_bwd2_kernel(const T* __restrict__ x,
   }
 }
 
-inline int n_blocks(long total) {
-  long b = (total + kBlock - 1) / kBlock;
-  return (int)std::min<long>(b, kGridCap);
-}
-
 hipStream_t cur_stream() {
   return at::hip::getCurrentHIPStream().stream();
 }
@@ -304,7 +301,8 @@ inline long row_elems(const torch::Tensor& t) {
 struct Operands {
   long E, N, F;
   PnaCfg cfg;
-  torch::Tensor rp, pc;
+  torch::Tensor rk, pk;
+  const long* rowptr;
   const long* perm;
 };
 
@@ -315,13 +313,12 @@ Operands check_operands(const torch::Tensor& x, const torch::Tensor& rowptr,
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
               "msg must be a contiguous GPU tensor");
   TORCH_CHECK(x.dim() >= 2, "msg needs a row and a feature dim");
-  TORCH_CHECK(rowptr.is_cuda() && rowptr.dtype() == torch::kLong &&
-                  rowptr.dim() == 1 && rowptr.numel() >= 1,
-              "rowptr must be int64 [N + 1] on the device");
   Operands o;
   o.E = x.size(0);
   o.N = rowptr.numel() - 1;
   o.F = row_elems(x);
+  o.rowptr = segment::rowptr_ptr(rowptr, o.N, o.rk);
+  o.perm = segment::index_ptr(perm, o.E, o.pk, "perm");
   TORCH_CHECK(o.E < (1L << 31), "pna_aggregate stores args as int32: "
               "E must be below 2^31");
   TORCH_CHECK(!aggs.empty() && (long)aggs.size() <= kMaxAgg,
@@ -348,15 +345,6 @@ Operands check_operands(const torch::Tensor& x, const torch::Tensor& rowptr,
   TORCH_CHECK(scale.scalar_type() == acc_type,
               "scale must be in the accumulator type");
   o.cfg.S = (int)scale.size(1);
-  o.rp = rowptr.contiguous();
-  o.perm = nullptr;
-  if (perm.has_value()) {
-    TORCH_CHECK(perm->is_cuda() && perm->dtype() == torch::kLong &&
-                    perm->numel() == o.E,
-                "perm must be int64 [E] on the device");
-    o.pc = perm->contiguous();
-    o.perm = o.pc.data_ptr<long>();
-  }
   return o;
 }
 
@@ -394,12 +382,12 @@ std::vector<torch::Tensor> pna_fwd(torch::Tensor x, torch::Tensor rowptr,
         hipLaunchKernelGGL((pna_fwd_kernel<scalar_t, acc_t>),
                            dim3(n_blocks(o.N * o.F)), dim3(kBlock), 0,
                            cur_stream(), x.data_ptr<scalar_t>(),
-                           o.rp.data_ptr<long>(), o.perm,
+                           o.rowptr, o.perm,
                            scale.data_ptr<acc_t>(),
                            out.data_ptr<scalar_t>(),
                            stats.data_ptr<acc_t>(), arg.data_ptr<int>(),
                            o.N, o.F, o.cfg);
-        C10_HIP_KERNEL_LAUNCH_CHECK();
+        check_launch("pna_fwd_kernel");
       });
   return {out, stats, arg};
 }
@@ -421,12 +409,12 @@ torch::Tensor pna_bwd(torch::Tensor x, torch::Tensor rowptr,
         hipLaunchKernelGGL((pna_bwd_kernel<scalar_t, acc_t>),
                            dim3(n_blocks(o.N * o.F)), dim3(kBlock), 0,
                            cur_stream(), x.data_ptr<scalar_t>(),
-                           o.rp.data_ptr<long>(), o.perm,
+                           o.rowptr, o.perm,
                            scale.data_ptr<acc_t>(),
                            stats.data_ptr<acc_t>(), arg.data_ptr<int>(),
                            G.data_ptr<scalar_t>(),
                            dx.data_ptr<scalar_t>(), o.N, o.F, o.cfg);
-        C10_HIP_KERNEL_LAUNCH_CHECK();
+        check_launch("pna_bwd_kernel");
       });
   return dx;
 }
@@ -463,14 +451,14 @@ std::vector<torch::Tensor> pna_bwd2(torch::Tensor x, torch::Tensor rowptr,
         hipLaunchKernelGGL((pna_bwd2_kernel<scalar_t, acc_t>),
                            dim3(n_blocks(o.N * o.F)), dim3(kBlock), 0,
                            cur_stream(), x.data_ptr<scalar_t>(),
-                           o.rp.data_ptr<long>(), o.perm,
+                           o.rowptr, o.perm,
                            scale.data_ptr<acc_t>(),
                            stats.data_ptr<acc_t>(), arg.data_ptr<int>(),
                            G.data_ptr<scalar_t>(), c.data_ptr<scalar_t>(),
                            need_G ? hG.data_ptr<scalar_t>() : nullptr,
                            need_x ? gx.data_ptr<scalar_t>() : nullptr,
                            o.N, o.F, o.cfg);
-        C10_HIP_KERNEL_LAUNCH_CHECK();
+        check_launch("pna_bwd2_kernel");
       });
   return {hG, gx};
 }

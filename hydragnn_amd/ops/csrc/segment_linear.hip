@@ -40,6 +40,7 @@
 // every run.
 
 #include <torch/extension.h>
+#include <ATen/OpMathType.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
@@ -48,9 +49,6 @@
 #include "check_launch.h"
 
 namespace {
-
-template <typename T> struct sl_acc { using type = float; };
-template <> struct sl_acc<double> { using type = double; };
 
 constexpr int SL_BLOCK = 256;
 constexpr int SL_R = 32;          // outer sum: rows per LDS tile
@@ -74,9 +72,9 @@ template <typename T, int PA, int QB>
 __global__ __launch_bounds__(SL_BLOCK) void seglin_outer_kernel(
     const T* __restrict__ A, const T* __restrict__ B,
     const long* __restrict__ ptr,
-    typename sl_acc<T>::type* __restrict__ out, long N, int H, int a,
+    at::opmath_type<T>* __restrict__ out, long N, int H, int a,
     int b) {
-  using ACC = typename sl_acc<T>::type;
+  using ACC = at::opmath_type<T>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int AP = 16 * PA, BP = 16 * QB;
   ACC* As = reinterpret_cast<ACC*>(smem);    // [SL_R][AP]
@@ -156,10 +154,10 @@ __global__ __launch_bounds__(SL_BLOCK) void seglin_zsum_kernel(
 
 template <typename T, int QO>
 __global__ __launch_bounds__(SL_BLOCK) void seglin_matvec_kernel(
-    const T* __restrict__ A, const typename sl_acc<T>::type* __restrict__ K,
+    const T* __restrict__ A, const at::opmath_type<T>* __restrict__ K,
     const long* __restrict__ ptr, T* __restrict__ O, long N, int H, int a,
     int b, int trans) {
-  using ACC = typename sl_acc<T>::type;
+  using ACC = at::opmath_type<T>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int win = trans ? b : a, wout = trans ? a : b;
   const int wp = win | 1;                    // odd row stride for As
@@ -270,7 +268,7 @@ hipStream_t sl_stream() {
 
 template <typename T, int PA>
 void launch_outer_qb(int qb, dim3 grid, size_t lds, const T* A, const T* B,
-                     const long* ptr, typename sl_acc<T>::type* out, long N,
+                     const long* ptr, at::opmath_type<T>* out, long N,
                      int H, int a, int b) {
 #define SL_OUTER(QB)                                                       \
   hipLaunchKernelGGL((seglin_outer_kernel<T, PA, QB>), grid,               \
@@ -287,7 +285,7 @@ void launch_outer_qb(int qb, dim3 grid, size_t lds, const T* A, const T* B,
 
 template <typename T>
 void launch_matvec(int qo, dim3 grid, size_t lds, const T* A,
-                   const typename sl_acc<T>::type* K, const long* ptr, T* O,
+                   const at::opmath_type<T>* K, const long* ptr, T* O,
                    long N, int H, int a, int b, int trans) {
 #define SL_MATVEC(QO)                                                      \
   hipLaunchKernelGGL((seglin_matvec_kernel<T, QO>), grid, dim3(SL_BLOCK),  \
@@ -351,7 +349,7 @@ torch::Tensor segment_outer_sum(torch::Tensor A, torch::Tensor B,
   const dim3 grid(G, H, Z);
   AT_DISPATCH_FLOATING_TYPES_AND(
       at::ScalarType::BFloat16, A.scalar_type(), "segment_outer_sum", [&] {
-        using ACC = typename sl_acc<scalar_t>::type;
+        using ACC = at::opmath_type<scalar_t>;
         ACC* out = (Z > 1 ? part : K).data_ptr<ACC>();
         const scalar_t* pa = A.data_ptr<scalar_t>();
         const scalar_t* pb = B.data_ptr<scalar_t>();
@@ -406,7 +404,7 @@ torch::Tensor segment_matvec(torch::Tensor A, torch::Tensor K,
   const dim3 grid(G, H, split_of(N, G, H, SL_BW));
   AT_DISPATCH_FLOATING_TYPES_AND(
       at::ScalarType::BFloat16, A.scalar_type(), "segment_matvec", [&] {
-        using ACC = typename sl_acc<scalar_t>::type;
+        using ACC = at::opmath_type<scalar_t>;
         launch_matvec<scalar_t>(qb_of(wout), grid, lds,
                                 A.data_ptr<scalar_t>(), K.data_ptr<ACC>(),
                                 ptr.data_ptr<long>(),

@@ -31,6 +31,7 @@
 // fixed order and rounds once.  Z depends on the host-known shapes only.
 
 #include <torch/extension.h>
+#include <ATen/OpMathType.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -38,9 +39,6 @@
 #include "check_launch.h"
 
 namespace {
-
-template <typename T> struct sc_acc { using type = float; };
-template <> struct sc_acc<double> { using type = double; };
 
 constexpr int SC_MAX_D = 9;      // D, Do
 constexpr int SC_MAX_P = 32;
@@ -69,7 +67,7 @@ __global__ void symcon_fwd_kernel(
     const int* __restrict__ ent, const float* __restrict__ coef, int K,
     long N, int C, int D, int Do, int P, int nel) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  using ACC = typename sc_acc<T>::type;
+  using ACC = at::opmath_type<T>;
   const int B = blockDim.x, tid = threadIdx.x;
   ACC* xs = reinterpret_cast<ACC*>(smem);       // [D+1][B]
   ACC* ws = xs + (size_t)(D + 1) * B;           // [P][B]
@@ -122,11 +120,11 @@ __global__ void symcon_grad_kernel(
     const T* __restrict__ t, const T* __restrict__ W,
     const long* __restrict__ perm, const long* __restrict__ rowptr,
     T* __restrict__ ox, T* __restrict__ og,
-    typename sc_acc<T>::type* __restrict__ partial,
+    at::opmath_type<T>* __restrict__ partial,
     const int* __restrict__ ent, const float* __restrict__ coef, int K,
     long N, int C, int D, int Do, int P, int ct_log2) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  using ACC = typename sc_acc<T>::type;
+  using ACC = at::opmath_type<T>;
   const int B = blockDim.x, tid = threadIdx.x;
   const int CT = 1 << ct_log2, R = B >> ct_log2;
   const int Z = gridDim.x, z = blockIdx.x, e = blockIdx.y;
@@ -236,10 +234,10 @@ __global__ void symcon_grad_kernel(
 constexpr int WS_PC = 16, WS_Z = 16;
 template <typename T>
 __global__ __launch_bounds__(WS_PC * WS_Z) void symcon_wsum_kernel(
-    const typename sc_acc<T>::type* __restrict__ partial,
+    const at::opmath_type<T>* __restrict__ partial,
     const long* __restrict__ rowptr, T* __restrict__ gW, long N, int PC,
     int Z, int R) {
-  using ACC = typename sc_acc<T>::type;
+  using ACC = at::opmath_type<T>;
   __shared__ ACC lanes[WS_PC * WS_Z];
   const int pl = threadIdx.x % WS_PC, zl = threadIdx.x / WS_PC;
   const long e = blockIdx.y;
@@ -421,7 +419,7 @@ std::vector<torch::Tensor> symcon_grad(
         x.options().dtype(dbl ? torch::kDouble : torch::kFloat));
   AT_DISPATCH_FLOATING_TYPES_AND(
       at::ScalarType::BFloat16, x.scalar_type(), "symcon_grad", [&] {
-        using ACC = typename sc_acc<scalar_t>::type;
+        using ACC = at::opmath_type<scalar_t>;
         auto ptr = [](torch::Tensor& o) -> scalar_t* {
           return o.defined() ? o.data_ptr<scalar_t>() : nullptr;
         };

@@ -19,7 +19,7 @@ product ``P = h [W_i ; W_j]^T``: the per-edge GEMM with K = 2F + 1 + D
 becomes a per-node GEMM with K = F, a gather, an add and a rank-(1 + D)
 update.
 
-``src`` and ``dst`` are the ``SegmentPlan``s of ``gather_mul``.  Every
+``src`` and ``dst`` are ``SegmentPlan``s (ops/segment_plan.py).  Every
 operand group is optional (``P``; ``r2`` with ``w_r``; ``ea`` with
 ``W_e``; ``b``): an absent group contributes nothing.  Semantics, the
 same on the HIP kernels (csrc/edge_affine.hip) and on the pure-torch
@@ -51,12 +51,11 @@ the doubles, counted as ``composition``.
 
 from __future__ import annotations
 
-import os
-
 import torch
 
-from ._extension import get_extension, use_eager
-from .gather_mul import SegmentPlan, _check_plans, acc_dtype
+from ._extension import get_extension
+from .segment_plan import (PathCounter, SegmentPlan, acc_dtype, check_plans,
+                           env_default, kernel_route)
 
 __all__ = ["edge_pair_affine", "pair_affine_node", "pair_affine_edge",
            "pair_affine_param", "torch_edge_pair_affine",
@@ -65,21 +64,18 @@ __all__ = ["edge_pair_affine", "pair_affine_node", "pair_affine_edge",
            "reset_path_counts", "MAX_EDGE_DIM"]
 
 MAX_EDGE_DIM = 16
-_KERNEL_DTYPES = (torch.float32, torch.float64, torch.bfloat16,
-                  torch.float16)
 
-_counts = {"fwd": 0, "node": 0, "edge": 0, "param": 0, "composition": 0}
+_counts = PathCounter("fwd", "node", "edge", "param", "composition")
 
 
 def path_counts() -> dict:
     """Launches per primitive (``param`` counts its two kernels as one),
     and calls that ran a torch double instead."""
-    return dict(_counts)
+    return _counts.snapshot()
 
 
 def reset_path_counts() -> None:
-    for k in _counts:
-        _counts[k] = 0
+    _counts.reset()
 
 
 def fused_egnn(default: bool) -> bool:
@@ -87,8 +83,7 @@ def fused_egnn(default: bool) -> bool:
     HYDRAGNN_EGNN_FUSED=0 restores the concatenation, any other value
     selects the fused route, and unset leaves the stack's own default
     (profiles/README.md).  Read at call time."""
-    value = os.environ.get("HYDRAGNN_EGNN_FUSED")
-    return default if value is None else value != "0"
+    return env_default("HYDRAGNN_EGNN_FUSED", default)
 
 
 # ---------------------------------------------------------------------------
@@ -153,8 +148,7 @@ def torch_pair_affine_param(g, r2, ea, bias=True):
 # dispatch
 # ---------------------------------------------------------------------------
 def _kernel_route(t, n_edges, edge_dim) -> bool:
-    return (t.is_cuda and not use_eager() and t.dtype in _KERNEL_DTYPES
-            and n_edges < 2 ** 31 and edge_dim <= MAX_EDGE_DIM)
+    return kernel_route(t, n_edges) and edge_dim <= MAX_EDGE_DIM
 
 
 def _c(t):
@@ -175,7 +169,7 @@ class _Fwd(torch.autograd.Function):
         ctx.plans = (src, dst)
         ctx.set_materialize_grads(False)
         like = next(t for t in (P, r2, ea, b) if t is not None)
-        _counts["fwd"] += 1
+        _counts.hit("fwd")
         return get_extension(required=True).pair_affine_fwd(
             P, r2, ea, w_r, None if W_e is None else W_e.t().contiguous(),
             b, None if P is None else dst.index,
@@ -208,7 +202,7 @@ class _Node(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         d_perm, d_rowptr = dst.csr()
         s_perm, s_rowptr = src.csr()
-        _counts["node"] += 1
+        _counts.hit("node")
         return get_extension(required=True).pair_affine_node(
             g, d_rowptr.contiguous(), _c(d_perm), s_rowptr.contiguous(),
             _c(s_perm), dst.size)
@@ -227,7 +221,7 @@ class _Edge(torch.autograd.Function):
     def forward(ctx, g, w_r, W_e):
         ctx.save_for_backward(g, w_r, W_e)
         ctx.set_materialize_grads(False)
-        _counts["edge"] += 1
+        _counts.hit("edge")
         dr2, dea = get_extension(required=True).pair_affine_edge(
             g, w_r, None if W_e is None else W_e.t().contiguous())
         return dr2, dea
@@ -259,7 +253,7 @@ class _Param(torch.autograd.Function):
     def forward(ctx, g, r2, ea, bias):
         ctx.save_for_backward(g, r2, ea)
         ctx.set_materialize_grads(False)
-        _counts["param"] += 1
+        _counts.hit("param")
         dwr, dWe, db = get_extension(required=True).pair_affine_param(
             g, r2, ea, bias)
         return dwr, dWe, db
@@ -340,7 +334,7 @@ def edge_pair_affine(P, r2, ea, w_r, W_e, b, src: SegmentPlan = None,
     if (ea is None) != (W_e is None):
         raise ValueError("ea and W_e go together")
     if P is not None:
-        _check_plans(src, dst)
+        check_plans(src, dst)
         n_edges = src.n_edges
     elif r2 is not None or ea is not None:
         n_edges = (r2 if r2 is not None else ea).shape[0]
@@ -358,7 +352,7 @@ def edge_pair_affine(P, r2, ea, w_r, W_e, b, src: SegmentPlan = None,
     if b is not None and tuple(b.shape) != (feat,):
         raise ValueError(f"b must be [{feat}], got {tuple(b.shape)}")
     if not _kernel_route(ref, n_edges, _width(ea)):
-        _counts["composition"] += 1
+        _counts.hit("composition")
         return torch_edge_pair_affine(P, r2, ea, w_r, W_e, b, src, dst,
                                       n_edges, like)
     if n_edges == 0 or feat == 0 or (P is not None and P.shape[0] == 0) \
@@ -371,14 +365,14 @@ def edge_pair_affine(P, r2, ea, w_r, W_e, b, src: SegmentPlan = None,
 def pair_affine_node(g: torch.Tensor, src: SegmentPlan,
                      dst: SegmentPlan) -> torch.Tensor:
     """dP[N, 2H]: the gradient of ``edge_pair_affine`` in ``P``."""
-    _check_plans(src, dst)
+    check_plans(src, dst)
     n_edges, feat = _check_g(g)
     if src.n_edges != n_edges:
         raise ValueError(f"g has {n_edges} rows for {src.n_edges} edges")
     if src.size != dst.size:
         raise ValueError(f"the plans have {src.size} and {dst.size} rows")
     if not _kernel_route(g, n_edges, 0):
-        _counts["composition"] += 1
+        _counts.hit("composition")
         return torch_pair_affine_node(g, src, dst)
     if n_edges == 0 or feat == 0 or dst.size == 0:
         return g.new_zeros(dst.size, 2 * feat)
@@ -399,7 +393,7 @@ def pair_affine_edge(g: torch.Tensor, w_r, W_e):
     if w_r is None and W_e is None:
         return None, None
     if not _kernel_route(g, n_edges, _width(W_e)):
-        _counts["composition"] += 1
+        _counts.hit("composition")
         return torch_pair_affine_edge(g, w_r, W_e)
     if n_edges == 0 or feat == 0:
         return (None if w_r is None else g.new_zeros(n_edges),
@@ -423,7 +417,7 @@ def pair_affine_param(g: torch.Tensor, r2, ea, bias: bool = True):
     if r2 is None and ea is None and not bias:
         return None, None, None
     if not _kernel_route(g, n_edges, _width(ea)):
-        _counts["composition"] += 1
+        _counts.hit("composition")
         return torch_pair_affine_param(g, r2, ea, bias)
     if n_edges == 0 or feat == 0:
         return (None if r2 is None else g.new_zeros(feat),

@@ -43,32 +43,26 @@ an ``index_add_`` in the accumulator type, one cast; no host sync.
 
 from __future__ import annotations
 
-import os
-from typing import Optional, Tuple
-
 import torch
 
-from ._extension import get_extension, use_eager
-from .scatter import _rowptr_from_sorted
+from ._extension import get_extension
+from .segment_plan import (PathCounter, SegmentPlan, acc_dtype,
+                           check_plans, env_default, kernel_route)
 
 __all__ = ["SegmentPlan", "gather_mul_sum", "gather_mul", "path_counts",
            "reset_path_counts"]
 
-_KERNEL_DTYPES = (torch.float32, torch.float64, torch.bfloat16,
-                  torch.float16)
-
-_counts = {"sum": 0, "mul": 0, "composition": 0}
+_counts = PathCounter("sum", "mul", "composition")
 
 
 def path_counts() -> dict:
     """Launches of the sum kernel and of the product kernel, and calls
     that ran a torch double instead."""
-    return dict(_counts)
+    return _counts.snapshot()
 
 
 def reset_path_counts() -> None:
-    for k in _counts:
-        _counts[k] = 0
+    _counts.reset()
 
 
 def fused_messages(default: bool) -> bool:
@@ -77,63 +71,7 @@ def fused_messages(default: bool) -> bool:
     fused route, and unset leaves the stack's own default (on where the
     end-to-end step measured no slower, see profiles/README.md).  Read at
     call time."""
-    value = os.environ.get("HYDRAGNN_GATHER_MUL")
-    return default if value is None else value != "0"
-
-
-def acc_dtype(dtype: torch.dtype) -> torch.dtype:
-    """fp32 for the half types, the dtype itself otherwise."""
-    return torch.float32 if dtype in (torch.bfloat16, torch.float16) \
-        else dtype
-
-
-class SegmentPlan:
-    """One grouping of E edges into ``size`` rows: ``index[e]`` is the
-    row of edge e.  ``csr()`` gives ``(perm | None, rowptr[size + 1])``
-    with ``perm = argsort(index, stable=True)`` (None for a sorted
-    index), built on first use and kept.  Nothing here syncs with the
-    host."""
-
-    def __init__(self, index: torch.Tensor, size: int,
-                 sorted_index: bool = False, _identity: bool = False):
-        if index.dim() != 1:
-            raise ValueError("index must be [E]")
-        if index.dtype != torch.long:
-            index = index.long()
-        self.index = index.contiguous()
-        self.size = int(size)
-        self.sorted_index = bool(sorted_index) or _identity
-        self.is_identity = _identity
-        self._csr: Optional[Tuple[Optional[torch.Tensor],
-                                  torch.Tensor]] = None
-
-    @classmethod
-    def from_index(cls, index: torch.Tensor, size: int,
-                   sorted_index: bool = False) -> "SegmentPlan":
-        return cls(index, size, sorted_index)
-
-    @classmethod
-    def identity(cls, n_edges: int, device=None) -> "SegmentPlan":
-        """index = arange(E): row e holds edge e alone."""
-        plan = cls(torch.arange(n_edges, device=device), n_edges,
-                   _identity=True)
-        plan._csr = (None, torch.arange(n_edges + 1, device=device))
-        return plan
-
-    @property
-    def n_edges(self) -> int:
-        return self.index.shape[0]
-
-    def csr(self):
-        if self._csr is None:
-            with torch.no_grad():
-                if self.sorted_index:
-                    perm, sidx = None, self.index
-                else:
-                    perm = torch.argsort(self.index, stable=True)
-                    sidx = self.index.index_select(0, perm)
-                self._csr = (perm, _rowptr_from_sorted(sidx, self.size))
-        return self._csr
+    return env_default("HYDRAGNN_GATHER_MUL", default)
 
 
 # ---------------------------------------------------------------------------
@@ -155,11 +93,6 @@ def torch_gather_mul(a, b, src: SegmentPlan, dst: SegmentPlan):
 # ---------------------------------------------------------------------------
 # dispatch
 # ---------------------------------------------------------------------------
-def _kernel_route(t, n_edges) -> bool:
-    return (t.is_cuda and not use_eager() and t.dtype in _KERNEL_DTYPES
-            and n_edges < 2 ** 31)
-
-
 def _gidx(plan: SegmentPlan):
     return None if plan.is_identity else plan.index
 
@@ -168,12 +101,12 @@ def _sum(x, w, src, dst):
     n_edges, feat = w.shape
     if n_edges == 0 or dst.size == 0 or feat == 0:
         return x.new_zeros(dst.size, feat)
-    if _kernel_route(x, n_edges):
+    if kernel_route(x, n_edges):
         perm, rowptr = dst.csr()
-        _counts["sum"] += 1
+        _counts.hit("sum")
         return get_extension(required=True).gather_mul_sum(
             x, w, _gidx(src), rowptr, perm)
-    _counts["composition"] += 1
+    _counts.hit("composition")
     return torch_gather_mul_sum(x, w, src, dst)
 
 
@@ -181,11 +114,11 @@ def _mul(a, b, src, dst):
     n_edges, feat = src.n_edges, a.shape[1]
     if n_edges == 0 or feat == 0:
         return a.new_empty(n_edges, feat)
-    if _kernel_route(a, n_edges):
-        _counts["mul"] += 1
+    if kernel_route(a, n_edges):
+        _counts.hit("mul")
         return get_extension(required=True).gather_mul(
             a, b, _gidx(src), _gidx(dst), n_edges)
-    _counts["composition"] += 1
+    _counts.hit("composition")
     return torch_gather_mul(a, b, src, dst)
 
 
@@ -242,19 +175,11 @@ def _flat(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.reshape(t.shape[0], feat).contiguous()
 
 
-def _check_plans(src, dst):
-    if not (isinstance(src, SegmentPlan) and isinstance(dst, SegmentPlan)):
-        raise TypeError("src and dst must be SegmentPlans")
-    if src.n_edges != dst.n_edges:
-        raise ValueError(
-            f"the plans group {src.n_edges} and {dst.n_edges} edges")
-
-
 def gather_mul_sum(x: torch.Tensor, w: torch.Tensor, src: SegmentPlan,
                    dst: SegmentPlan) -> torch.Tensor:
     """out[dst.size, ...] = sum over the edges of each dst row of
     x[src.index[e]] * w[e].  See the module docstring."""
-    _check_plans(src, dst)
+    check_plans(src, dst)
     if x.dtype != w.dtype:
         raise ValueError(f"x is {x.dtype} and w is {w.dtype}")
     if x.shape[1:] != w.shape[1:]:
@@ -272,7 +197,7 @@ def gather_mul(a: torch.Tensor, b: torch.Tensor, src: SegmentPlan,
                dst: SegmentPlan) -> torch.Tensor:
     """out[E, ...] = a[src.index[e]] * b[dst.index[e]].  See the module
     docstring."""
-    _check_plans(src, dst)
+    check_plans(src, dst)
     if a.dtype != b.dtype:
         raise ValueError(f"a is {a.dtype} and b is {b.dtype}")
     if a.shape[1:] != b.shape[1:]:

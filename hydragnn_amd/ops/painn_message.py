@@ -12,7 +12,7 @@ source vector, gate on the edge direction, scalar message):
                                 + (w1[e, f] phi1[j, f]) u[e, d])
     ds[i, f]    = sum_{e -> i}   w2[e, f] phi2[j, f]
 
-``src`` and ``dst`` are the ``SegmentPlan``s of ``gather_mul``.  The
+``src`` and ``dst`` are ``SegmentPlan``s (ops/segment_plan.py).  The
 semantics are those of ``gather_mul_sum``: the sum runs in ascending
 edge id within a row, from 0, in the accumulator type (fp32 for
 bf16/f16/fp32, fp64 for fp64); every product is rounded to the
@@ -37,33 +37,28 @@ counted as ``composition``.
 
 from __future__ import annotations
 
-import os
-
 import torch
 
-from ._extension import get_extension, use_eager
-from .gather_mul import SegmentPlan, _check_plans, acc_dtype
+from ._extension import get_extension
 from .scatter import gather, scatter
+from .segment_plan import (PathCounter, SegmentPlan, acc_dtype, check_plans,
+                           env_default, kernel_route)
 
 __all__ = ["painn_message", "torch_painn_message",
            "torch_painn_message_bwd", "fused_painn", "path_counts",
            "reset_path_counts"]
 
-_KERNEL_DTYPES = (torch.float32, torch.float64, torch.bfloat16,
-                  torch.float16)
-
-_counts = {"fwd": 0, "bwd_node": 0, "bwd_edge": 0, "composition": 0}
+_counts = PathCounter("fwd", "bwd_node", "bwd_edge", "composition")
 
 
 def path_counts() -> dict:
     """Launches of the three kernels, and calls that ran a torch double
     instead (the second order among them)."""
-    return dict(_counts)
+    return _counts.snapshot()
 
 
 def reset_path_counts() -> None:
-    for k in _counts:
-        _counts[k] = 0
+    _counts.reset()
 
 
 def fused_painn(default: bool) -> bool:
@@ -71,8 +66,7 @@ def fused_painn(default: bool) -> bool:
     HYDRAGNN_PAINN_FUSED=0 restores the composition of generic ops, any
     other value selects the fused route, and unset leaves the stack's
     own default (profiles/README.md).  Read at call time."""
-    value = os.environ.get("HYDRAGNN_PAINN_FUSED")
-    return default if value is None else value != "0"
+    return env_default("HYDRAGNN_PAINN_FUSED", default)
 
 
 # ---------------------------------------------------------------------------
@@ -134,11 +128,6 @@ def torch_painn_message_bwd(phi, w, v, u, gs, gv, src: SegmentPlan,
 # ---------------------------------------------------------------------------
 # dispatch
 # ---------------------------------------------------------------------------
-def _kernel_route(t, n_edges) -> bool:
-    return (t.is_cuda and not use_eager() and t.dtype in _KERNEL_DTYPES
-            and n_edges < 2 ** 31)
-
-
 def _nothing(phi, w) -> bool:
     return w.shape[0] == 0 or phi.shape[0] == 0 or phi.shape[1] == 0
 
@@ -156,7 +145,7 @@ class _PainnMessage(torch.autograd.Function):
             dv = phi.new_zeros(phi.shape[0], 3 * feat)
             return (phi.new_zeros(phi.shape[0], feat) if scalar else None), dv
         perm, rowptr = dst.csr()
-        _counts["fwd"] += 1
+        _counts.hit("fwd")
         ds, dv = get_extension(required=True).painn_msg_fwd(
             phi, w, v, u, src.index, rowptr, perm, scalar)
         return ds, dv
@@ -194,12 +183,12 @@ class _PainnMessageBwd(torch.autograd.Function):
         ext = get_extension(required=True)
         if need[0] or need[2]:
             perm, rowptr = src.csr()
-            _counts["bwd_node"] += 1
+            _counts.hit("bwd_node")
             dphi, dv_in = ext.painn_msg_bwd_node(
                 phi, w, v, u, gs, gv, dst.index, rowptr, perm, need[0],
                 need[2])
         if need[1] or need[3]:
-            _counts["bwd_edge"] += 1
+            _counts.hit("bwd_edge")
             dw, du = ext.painn_msg_bwd_edge(
                 phi, w, v, u, gs, gv, src.index, dst.index, need[1], need[3])
         return dphi, dw, dv_in, du
@@ -214,7 +203,7 @@ class _PainnMessageBwd(torch.autograd.Function):
                   if ctx.needs_input_grad[k] and saved[k] is not None]
         grads = [None] * 6
         if picked and wanted:
-            _counts["composition"] += 1
+            _counts.hit("composition")
             create = torch.is_grad_enabled()
             with torch.enable_grad():
                 # aliases: the cotangents are themselves functions of
@@ -240,7 +229,7 @@ def painn_message(phi: torch.Tensor, w: torch.Tensor, v: torch.Tensor,
                   u: torch.Tensor, src: SegmentPlan, dst: SegmentPlan,
                   scalar: bool = True):
     """(ds[N, F] | None, dv[N, 3, F]).  See the module docstring."""
-    _check_plans(src, dst)
+    check_plans(src, dst)
     if v.dim() != 3 or v.shape[1] != 3:
         raise ValueError(f"v must be [N, 3, F], got {tuple(v.shape)}")
     n, _, feat = v.shape
@@ -259,8 +248,8 @@ def painn_message(phi: torch.Tensor, w: torch.Tensor, v: torch.Tensor,
     if src.size != n or dst.size != n:
         raise ValueError(f"the plans have {src.size} and {dst.size} rows "
                          f"for {n} nodes")
-    if not _kernel_route(phi, n_edges):
-        _counts["composition"] += 1
+    if not kernel_route(phi, n_edges):
+        _counts.hit("composition")
         return torch_painn_message(phi, w, v, u, src, dst, scalar)
     ds, dv = _PainnMessage.apply(
         phi.contiguous(), w.contiguous(),

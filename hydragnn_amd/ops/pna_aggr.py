@@ -45,7 +45,9 @@ from typing import Optional, Sequence
 
 import torch
 
-from ._extension import get_extension, use_eager
+from ._extension import get_extension
+from .segment_plan import (KERNEL_DTYPES, PathCounter,  # noqa: F401
+                           acc_dtype, env_default, kernel_route)
 
 __all__ = ["pna_aggregate", "pna_scale", "path_counts",
            "reset_path_counts", "AGGREGATORS", "SCALERS"]
@@ -56,10 +58,8 @@ SCALERS = ("identity", "amplification", "attenuation", "linear",
 STD_EPS = 1e-5
 MAX_SCALERS = 8
 _SUM, _MEAN, _MIN, _MAX, _STD, _VAR = range(6)
-_KERNEL_DTYPES = (torch.float32, torch.float64, torch.bfloat16,
-                  torch.float16)
 
-_counts = {"fwd": 0, "bwd": 0, "bwd2": 0, "composition": 0}
+_counts = PathCounter("fwd", "bwd", "bwd2", "composition")
 
 
 def path_counts() -> dict:
@@ -67,22 +67,22 @@ def path_counts() -> dict:
     calls that ran a torch composition instead (the doubles below, the
     third-order fallback, or the module's aggregator-by-aggregator
     path)."""
-    return dict(_counts)
+    return _counts.snapshot()
 
 
 def reset_path_counts() -> None:
-    for k in _counts:
-        _counts[k] = 0
+    _counts.reset()
 
 
 def count_composition() -> None:
-    _counts["composition"] += 1
+    _counts.hit("composition")
 
 
-def acc_dtype(dtype: torch.dtype) -> torch.dtype:
-    """fp32 for the half types, the dtype itself otherwise."""
-    return torch.float32 if dtype in (torch.bfloat16, torch.float16) \
-        else dtype
+def fused_pna() -> bool:
+    """Whether ``DegreeScalerAggregation`` takes the fused op:
+    HYDRAGNN_PNA_FUSED=0 restores the aggregator-by-aggregator path.
+    Read at call time."""
+    return env_default("HYDRAGNN_PNA_FUSED", True)
 
 
 def aggregator_ids(aggregators: Sequence[str]):
@@ -331,38 +331,36 @@ def torch_pna_bwd2(msg, rowptr, perm, scale, aggs, stats, arg, G, c,
 # dispatch of the three entry points
 # ---------------------------------------------------------------------------
 def _kernel_route(msg, scale) -> bool:
-    return (msg.is_cuda and not use_eager()
-            and msg.dtype in _KERNEL_DTYPES
-            and msg.shape[0] < 2 ** 31 and msg.shape[0] > 0
+    return (kernel_route(msg, msg.shape[0]) and msg.shape[0] > 0
             and scale.shape[0] > 0 and scale.shape[1] <= MAX_SCALERS)
 
 
 def _fwd(msg, rowptr, perm, scale, aggs):
     if _kernel_route(msg, scale):
-        _counts["fwd"] += 1
+        _counts.hit("fwd")
         return get_extension(required=True).pna_fwd(
             msg, rowptr, perm, scale, list(aggs))
-    _counts["composition"] += 1
+    _counts.hit("composition")
     return torch_pna_fwd(msg, rowptr, perm, scale, aggs)
 
 
 def _bwd(msg, rowptr, perm, scale, aggs, stats, arg, G):
     if _kernel_route(msg, scale):
-        _counts["bwd"] += 1
+        _counts.hit("bwd")
         return get_extension(required=True).pna_bwd(
             msg, rowptr, perm, scale, list(aggs), stats, arg, G)
-    _counts["composition"] += 1
+    _counts.hit("composition")
     return torch_pna_bwd(msg, rowptr, perm, scale, aggs, stats, arg, G)
 
 
 def _bwd2(msg, rowptr, perm, scale, aggs, stats, arg, G, c, need_G,
           need_x):
     if _kernel_route(msg, scale):
-        _counts["bwd2"] += 1
+        _counts.hit("bwd2")
         return get_extension(required=True).pna_bwd2(
             msg, rowptr, perm, scale, list(aggs), stats, arg, G, c,
             need_G, need_x)
-    _counts["composition"] += 1
+    _counts.hit("composition")
     return torch_pna_bwd2(msg, rowptr, perm, scale, aggs, stats, arg, G, c,
                           need_G, need_x)
 
@@ -413,7 +411,7 @@ class _PNAAggrBwd(torch.autograd.Function):
         # third order: mu and v are recomputed from msg, so autograd
         # sees their dependence; the args are piecewise constant.  G
         # enters as a leaf: its own history is the caller's graph's.
-        _counts["composition"] += 1
+        _counts.hit("composition")
         with torch.enable_grad():
             x = msg if msg.requires_grad else \
                 msg.detach().requires_grad_(True)

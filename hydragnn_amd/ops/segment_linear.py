@@ -40,6 +40,7 @@ from typing import Optional
 import torch
 
 from ._extension import get_extension, use_eager
+from .segment_plan import acc_dtype
 
 _KERNEL_DTYPES = (torch.float32, torch.bfloat16, torch.float64)
 _LDS_BUDGET = 160 * 1024
@@ -48,12 +49,6 @@ MAX_A, MAX_B = 128, 132
 # how often each entry point ran (tests read this to see which one served)
 segment_linear_stats = {"outer": 0, "matvec": 0, "torch_outer": 0,
                         "torch_matvec": 0}
-
-
-def acc_dtype(dtype: torch.dtype) -> torch.dtype:
-    """The accumulator type of a row dtype: the dtype of every segment
-    matrix."""
-    return torch.float64 if dtype == torch.float64 else torch.float32
 
 
 def segment_linear_ok(a: int, b: int, tensor: torch.Tensor) -> bool:

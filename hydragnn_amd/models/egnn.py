@@ -16,7 +16,8 @@ from torch import nn
 from torch.nn import functional as F
 
 from ..ops import act_linear as al
-from ..ops.edge_affine import MAX_EDGE_DIM, edge_pair_affine, fused_egnn
+from ..ops.edge_affine import (MAX_EDGE_DIM, edge_pair_affine, fused_egnn,
+                               wide_envelope)
 from ..ops.segment_plan import SegmentPlan
 from ..ops.mfma_linear import (MFMALinear, _bf16_ok, _eligible,
                                mfma_linear_bf16)
@@ -85,6 +86,22 @@ class E_GCL(nn.Module):
                 z, lin2.weight.to(dt), None if bias is None else bias.to(dt)))
         return self.edge_mlp[3](lin2(act(z)))
 
+    def _wide_kernels(self, h, edge_dim):
+        """Whether `_fused_edge_mlp` would run the MFMA pair-affine
+        kernels on edge attributes wider than MAX_EDGE_DIM: a device
+        tensor, not forced eager, `P` in bf16 or f16, (H, D) inside
+        `wide_envelope`.  Anything else would land on the torch doubles
+        and keeps the concatenation."""
+        if not h.is_cuda or use_eager():
+            return False
+        if _bf16_ok(h):              # mfma_linear_bf16 or a bf16 F.linear
+            dt = torch.bfloat16
+        elif torch.is_autocast_enabled():
+            dt = torch.get_autocast_dtype("cuda")
+        else:
+            dt = h.dtype
+        return wide_envelope(dt, self.edge_mlp[0].out_features, edge_dim)
+
     def forward(self, h, pos, edge_index, edge_attr=None, edge_shifts=None,
                 plans=None):
         src, dst = edge_index[0], edge_index[1]
@@ -92,7 +109,8 @@ class E_GCL(nn.Module):
                                                     edge_shifts)
         r2 = (lengths ** 2)
         edge_dim = 0 if edge_attr is None else edge_attr.shape[-1]
-        if fused_egnn(FUSED_BY_DEFAULT) and edge_dim <= MAX_EDGE_DIM:
+        if fused_egnn(FUSED_BY_DEFAULT) and (
+                edge_dim <= MAX_EDGE_DIM or self._wide_kernels(h, edge_dim)):
             m = self._fused_edge_mlp(h, r2, edge_attr, edge_index, plans)
         else:
             hi = gather(h, dst)

@@ -569,6 +569,32 @@ long pair_affine_param_chunks(long E) {
       1, std::min<long>(kMaxChunks, (E + kChunkUnit - 1) / kChunkUnit));
 }
 
+// dw_r[H], dW_e[H, D] and db[H] from partial[n_chunks, 2 + D, H] in the
+// accumulator type, chunks in ascending order, rounded once; an
+// undefined output is skipped.  The second kernel of pair_affine_param,
+// also of the wide route (edge_affine_mfma.hip).
+void pair_affine_param_reduce(const torch::Tensor& partial,
+                              torch::Tensor& dwr, torch::Tensor& dWe,
+                              torch::Tensor& db, long H, long D,
+                              long n_chunks) {
+  const torch::Tensor& any = dwr.defined() ? dwr : (dWe.defined() ? dWe : db);
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  AT_DISPATCH_FLOATING_TYPES_AND2(
+      at::ScalarType::BFloat16, at::ScalarType::Half, any.scalar_type(),
+      "pair_affine_param_reduce", [&] {
+        using acc_t = at::opmath_type<scalar_t>;
+        hipLaunchKernelGGL(
+            (pair_affine_param_reduce_kernel<scalar_t, acc_t>),
+            dim3(n_blocks((2 + D) * H)), dim3(kBlock), 0, stream,
+            partial.data_ptr<acc_t>(),
+            dwr.defined() ? dwr.data_ptr<scalar_t>() : nullptr,
+            D > 0 && dWe.defined() ? dWe.data_ptr<scalar_t>() : nullptr,
+            db.defined() ? db.data_ptr<scalar_t>() : nullptr, H, (int)D,
+            n_chunks);
+        check_launch("pair_affine_param_reduce_kernel");
+      });
+}
+
 // (dw_r[H], dW_e[H, D], db[H]); dw_r and dW_e are undefined when r2 or
 // ea is absent, db when want_bias is false
 std::vector<torch::Tensor> pair_affine_param(torch::Tensor g, OptTensor r2,
@@ -622,14 +648,7 @@ std::vector<torch::Tensor> pair_affine_param(torch::Tensor g, OptTensor r2,
         else
           launch(pair_affine_param_kernel<scalar_t, acc_t, kMaxD>);
         check_launch("pair_affine_param_kernel");
-        hipLaunchKernelGGL(
-            (pair_affine_param_reduce_kernel<scalar_t, acc_t>),
-            dim3(n_blocks((2 + D) * H)), dim3(kBlock), 0, stream, pp,
-            r2.has_value() ? dwr.data_ptr<scalar_t>() : nullptr,
-            D > 0 ? dWe.data_ptr<scalar_t>() : nullptr,
-            want_bias ? db.data_ptr<scalar_t>() : nullptr, H, (int)D,
-            n_chunks);
-        check_launch("pair_affine_param_reduce_kernel");
+        pair_affine_param_reduce(partial, dwr, dWe, db, H, D, n_chunks);
       });
   return {dwr, dWe, db};
 }

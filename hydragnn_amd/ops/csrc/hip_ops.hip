@@ -806,6 +806,18 @@ std::vector<torch::Tensor> pair_affine_param(
     c10::optional<torch::Tensor> ea, bool want_bias);
 long pair_affine_param_chunks(long E);
 
+// defined in edge_affine_mfma.hip
+torch::Tensor pair_affine_wide_fwd(
+    c10::optional<torch::Tensor> P, c10::optional<torch::Tensor> r2,
+    torch::Tensor ea, c10::optional<torch::Tensor> wr, torch::Tensor We,
+    c10::optional<torch::Tensor> b, c10::optional<torch::Tensor> didx,
+    c10::optional<torch::Tensor> sidx, long E, long H);
+std::vector<torch::Tensor> pair_affine_wide_edge(
+    torch::Tensor g, c10::optional<torch::Tensor> wr, torch::Tensor weT);
+std::vector<torch::Tensor> pair_affine_wide_param(
+    torch::Tensor g, c10::optional<torch::Tensor> r2, torch::Tensor ea,
+    bool want_bias);
+
 // defined in act_linear.hip
 torch::Tensor act_linear_fwd(torch::Tensor h, torch::Tensor W,
                              c10::optional<torch::Tensor> bias);
@@ -865,6 +877,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("want_bias"));
   m.def("pair_affine_param_chunks", &pair_affine_param_chunks,
         "E-chunks of a pair_affine_param launch: a function of E alone");
+  m.def("pair_affine_wide_fwd", &pair_affine_wide_fwd,
+        "pair_affine_fwd for bf16/f16 with D % 32 == 0 in [32, 128] and "
+        "H % 64 == 0 in [64, 256]: the ea W_e^T term on MFMA; W_e is [H, D] "
+        "(HIP)",
+        pybind11::arg("P"), pybind11::arg("r2"), pybind11::arg("ea"),
+        pybind11::arg("wr"), pybind11::arg("We"), pybind11::arg("b"),
+        pybind11::arg("didx"), pybind11::arg("sidx"), pybind11::arg("E"),
+        pybind11::arg("H"));
+  m.def("pair_affine_wide_edge", &pair_affine_wide_edge,
+        "(dr2 | None, dea) = (g w_r, g W_e) per edge on MFMA, same "
+        "envelope; weT is W_e^T [D, H] (HIP)",
+        pybind11::arg("g"), pybind11::arg("wr"), pybind11::arg("weT"));
+  m.def("pair_affine_wide_param", &pair_affine_wide_param,
+        "(dw_r | None, dW_e, db | None) on MFMA, same envelope (HIP)",
+        pybind11::arg("g"), pybind11::arg("r2"), pybind11::arg("ea"),
+        pybind11::arg("want_bias"));
   m.def("gather_mul_sum", &gather_mul_sum,
         "out[i] = sum over CSR row i of x[gidx[e]] * w[e] (HIP); an "
         "absent gidx is the identity",

@@ -45,8 +45,19 @@ the kernels:
 The kernels serve device tensors of fp32, fp64, bf16 and f16 (all
 operands of one dtype) with any H, 0 <= D <= 16 and E < 2^31; E = 0 or
 N = 0 launches nothing; nothing syncs with the host.  CPU tensors,
-``HYDRAGNN_AMD_FORCE_EAGER=1`` and anything outside that envelope run
-the doubles, counted as ``composition``.
+``HYDRAGNN_AMD_FORCE_EAGER=1`` and anything outside that envelope and
+the wide one below run the doubles, counted as ``composition``.
+
+Wide edge attributes (csrc/edge_affine_mfma.hip, ``wide_envelope``):
+bf16 or f16 with D a multiple of 32 in [32, 128] and H a multiple of 64
+in [64, 256] run ``fwd``, ``edge`` and ``param`` on the matrix cores,
+the route chosen per call, so the closure table holds for them as well.
+Their contract: products of two bf16 or f16 values are exact in fp32;
+every sum is in fp32 and rounded once; the order of a D-, H- or E-sum
+is the matrix unit's and the tiling's, fixed per (shape, kernel) and
+not "k ascending", so results are reproducible run to run and equal the
+fp64 result rounded once whenever all partial sums are exact; nothing
+syncs with the host, E = 0 launches nothing, every launch is checked.
 """
 
 from __future__ import annotations
@@ -61,7 +72,7 @@ __all__ = ["edge_pair_affine", "pair_affine_node", "pair_affine_edge",
            "pair_affine_param", "torch_edge_pair_affine",
            "torch_pair_affine_node", "torch_pair_affine_edge",
            "torch_pair_affine_param", "fused_egnn", "path_counts",
-           "reset_path_counts", "MAX_EDGE_DIM"]
+           "reset_path_counts", "MAX_EDGE_DIM", "wide_envelope"]
 
 MAX_EDGE_DIM = 16
 
@@ -147,8 +158,16 @@ def torch_pair_affine_param(g, r2, ea, bias=True):
 # ---------------------------------------------------------------------------
 # dispatch
 # ---------------------------------------------------------------------------
-def _kernel_route(t, n_edges, edge_dim) -> bool:
-    return kernel_route(t, n_edges) and edge_dim <= MAX_EDGE_DIM
+def wide_envelope(dtype: torch.dtype, feat: int, edge_dim: int) -> bool:
+    """Whether (dtype, H, D) is served by the MFMA kernels."""
+    return (dtype in (torch.bfloat16, torch.float16)
+            and edge_dim % 32 == 0 and 32 <= edge_dim <= 128
+            and feat % 64 == 0 and 64 <= feat <= 256)
+
+
+def _kernel_route(t, n_edges, feat, edge_dim) -> bool:
+    return kernel_route(t, n_edges) and (
+        edge_dim <= MAX_EDGE_DIM or wide_envelope(t.dtype, feat, edge_dim))
 
 
 def _c(t):
@@ -170,6 +189,10 @@ class _Fwd(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         like = next(t for t in (P, r2, ea, b) if t is not None)
         _counts.hit("fwd")
+        if wide_envelope(like.dtype, shape[1], _width(ea)):
+            return get_extension(required=True).pair_affine_wide_fwd(
+                P, r2, ea, w_r, W_e, b, None if P is None else dst.index,
+                None if P is None else src.index, shape[0], shape[1])
         return get_extension(required=True).pair_affine_fwd(
             P, r2, ea, w_r, None if W_e is None else W_e.t().contiguous(),
             b, None if P is None else dst.index,
@@ -222,8 +245,11 @@ class _Edge(torch.autograd.Function):
         ctx.save_for_backward(g, w_r, W_e)
         ctx.set_materialize_grads(False)
         _counts.hit("edge")
-        dr2, dea = get_extension(required=True).pair_affine_edge(
-            g, w_r, None if W_e is None else W_e.t().contiguous())
+        ext = get_extension(required=True)
+        call = ext.pair_affine_wide_edge if wide_envelope(
+            g.dtype, g.shape[1], _width(W_e)) else ext.pair_affine_edge
+        dr2, dea = call(g, w_r,
+                        None if W_e is None else W_e.t().contiguous())
         return dr2, dea
 
     @staticmethod
@@ -254,8 +280,10 @@ class _Param(torch.autograd.Function):
         ctx.save_for_backward(g, r2, ea)
         ctx.set_materialize_grads(False)
         _counts.hit("param")
-        dwr, dWe, db = get_extension(required=True).pair_affine_param(
-            g, r2, ea, bias)
+        ext = get_extension(required=True)
+        call = ext.pair_affine_wide_param if wide_envelope(
+            g.dtype, g.shape[1], _width(ea)) else ext.pair_affine_param
+        dwr, dWe, db = call(g, r2, ea, bias)
         return dwr, dWe, db
 
     @staticmethod
@@ -351,7 +379,7 @@ def edge_pair_affine(P, r2, ea, w_r, W_e, b, src: SegmentPlan = None,
     r2 = _check_edge_groups(n_edges, feat, r2, ea, w_r, W_e)
     if b is not None and tuple(b.shape) != (feat,):
         raise ValueError(f"b must be [{feat}], got {tuple(b.shape)}")
-    if not _kernel_route(ref, n_edges, _width(ea)):
+    if not _kernel_route(ref, n_edges, feat, _width(ea)):
         _counts.hit("composition")
         return torch_edge_pair_affine(P, r2, ea, w_r, W_e, b, src, dst,
                                       n_edges, like)
@@ -371,7 +399,7 @@ def pair_affine_node(g: torch.Tensor, src: SegmentPlan,
         raise ValueError(f"g has {n_edges} rows for {src.n_edges} edges")
     if src.size != dst.size:
         raise ValueError(f"the plans have {src.size} and {dst.size} rows")
-    if not _kernel_route(g, n_edges, 0):
+    if not _kernel_route(g, n_edges, feat, 0):
         _counts.hit("composition")
         return torch_pair_affine_node(g, src, dst)
     if n_edges == 0 or feat == 0 or dst.size == 0:
@@ -392,7 +420,7 @@ def pair_affine_edge(g: torch.Tensor, w_r, W_e):
                          f"{tuple(W_e.shape)}")
     if w_r is None and W_e is None:
         return None, None
-    if not _kernel_route(g, n_edges, _width(W_e)):
+    if not _kernel_route(g, n_edges, feat, _width(W_e)):
         _counts.hit("composition")
         return torch_pair_affine_edge(g, w_r, W_e)
     if n_edges == 0 or feat == 0:
@@ -416,7 +444,7 @@ def pair_affine_param(g: torch.Tensor, r2, ea, bias: bool = True):
                          f"{tuple(ea.shape)}")
     if r2 is None and ea is None and not bias:
         return None, None, None
-    if not _kernel_route(g, n_edges, _width(ea)):
+    if not _kernel_route(g, n_edges, feat, _width(ea)):
         _counts.hit("composition")
         return torch_pair_affine_param(g, r2, ea, bias)
     if n_edges == 0 or feat == 0:

@@ -19,12 +19,34 @@ from torch import nn
 
 from ..ops import gather, get_edge_vectors_and_lengths, scatter
 from ..ops.gather_mul import SegmentPlan, fused_messages, gather_mul_sum
+from ..ops.splitk_linear import (_SplitKLinearFn, wgrad_kernel_enabled,
+                                 wgrad_route)
 from .base import Base
 
 # On unless HYDRAGNN_GATHER_MUL=0: dimenet_fp64 measured 1.2% faster
 # with the fused sums, and reproducible (profiles/README.md).
 FUSED_BY_DEFAULT = True
+# On unless HYDRAGNN_WGRAD_KERNEL=0: the weight-gradient kernel of the
+# edge-row and triplet-row layers took dimenet_fp64 from 384.5 ms to
+# 21.3 ms a step, slowest run against fastest (profiles/README.md).
+WGRAD_BY_DEFAULT = True
 from .pna_plus import BesselBasisLayer
+
+
+class RowLinear(nn.Linear):
+    """nn.Linear over rows that are edges or triplets: thousands to
+    millions of rows into a weight of a few tiles.  Where the
+    weight-gradient kernel is on and its route applies, the layer runs as
+    the split-K Function, whose backward takes dW (and db) from
+    csrc/wgrad.hip; otherwise it is nn.Linear's own path."""
+
+    def forward(self, x):
+        if (x.dim() == 2 and wgrad_kernel_enabled(WGRAD_BY_DEFAULT)
+                and x.dtype == self.weight.dtype
+                and wgrad_route(x, self.out_features)):
+            return _SplitKLinearFn.apply(x, self.weight, self.bias,
+                                         WGRAD_BY_DEFAULT)
+        return nn.functional.linear(x, self.weight, self.bias)
 
 
 def triplets(edge_index: torch.Tensor, num_nodes: int):
@@ -151,8 +173,8 @@ class HydraEmbeddingBlock(nn.Module):
     def __init__(self, in_dim: int, hidden: int, num_radial: int):
         super().__init__()
         self.lin_x = nn.Linear(in_dim, hidden)
-        self.lin_rbf = nn.Linear(num_radial, hidden)
-        self.lin = nn.Linear(3 * hidden, hidden)
+        self.lin_rbf = RowLinear(num_radial, hidden)
+        self.lin = RowLinear(3 * hidden, hidden)
         self.act = nn.SiLU()
 
     def forward(self, x, rbf, edge_index, plans=None):
@@ -172,8 +194,8 @@ class HydraEmbeddingBlock(nn.Module):
 class ResidualLayer(nn.Module):
     def __init__(self, hidden: int):
         super().__init__()
-        self.lin1 = nn.Linear(hidden, hidden)
-        self.lin2 = nn.Linear(hidden, hidden)
+        self.lin1 = RowLinear(hidden, hidden)
+        self.lin2 = RowLinear(hidden, hidden)
         self.act = nn.SiLU()
 
     def forward(self, x):
@@ -186,18 +208,18 @@ class InteractionPPBlock(nn.Module):
                  num_before_skip: int, num_after_skip: int):
         super().__init__()
         self.act = nn.SiLU()
-        self.lin_rbf1 = nn.Linear(num_radial, basis_emb_size, bias=False)
-        self.lin_rbf2 = nn.Linear(basis_emb_size, hidden, bias=False)
-        self.lin_sbf1 = nn.Linear(num_spherical * num_radial,
+        self.lin_rbf1 = RowLinear(num_radial, basis_emb_size, bias=False)
+        self.lin_rbf2 = RowLinear(basis_emb_size, hidden, bias=False)
+        self.lin_sbf1 = RowLinear(num_spherical * num_radial,
                                   basis_emb_size, bias=False)
-        self.lin_sbf2 = nn.Linear(basis_emb_size, int_emb_size, bias=False)
-        self.lin_kj = nn.Linear(hidden, hidden)
-        self.lin_ji = nn.Linear(hidden, hidden)
-        self.lin_down = nn.Linear(hidden, int_emb_size, bias=False)
-        self.lin_up = nn.Linear(int_emb_size, hidden, bias=False)
+        self.lin_sbf2 = RowLinear(basis_emb_size, int_emb_size, bias=False)
+        self.lin_kj = RowLinear(hidden, hidden)
+        self.lin_ji = RowLinear(hidden, hidden)
+        self.lin_down = RowLinear(hidden, int_emb_size, bias=False)
+        self.lin_up = RowLinear(int_emb_size, hidden, bias=False)
         self.before_skip = nn.ModuleList(
             [ResidualLayer(hidden) for _ in range(num_before_skip)])
-        self.lin = nn.Linear(hidden, hidden)
+        self.lin = RowLinear(hidden, hidden)
         self.after_skip = nn.ModuleList(
             [ResidualLayer(hidden) for _ in range(num_after_skip)])
 
@@ -229,7 +251,7 @@ class OutputPPBlock(nn.Module):
                  num_radial: int):
         super().__init__()
         self.act = nn.SiLU()
-        self.lin_rbf = nn.Linear(num_radial, hidden, bias=False)
+        self.lin_rbf = RowLinear(num_radial, hidden, bias=False)
         self.lin_up = nn.Linear(hidden, out_emb, bias=False)
         self.lins = nn.ModuleList([nn.Linear(out_emb, out_emb)
                                    for _ in range(2)])

@@ -832,7 +832,24 @@ std::vector<torch::Tensor> act_linear_wgrad(
     bool act, bool want_bias);
 long act_linear_wgrad_chunks(long E);
 
+// defined in wgrad.hip
+std::vector<torch::Tensor> linear_wgrad(torch::Tensor g, torch::Tensor x,
+                                        bool want_bias);
+long linear_wgrad_chunks(long E, long N, long K);
+long linear_wgrad_chunk_rows(long E, long N, long K);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("linear_wgrad", &linear_wgrad,
+        "(gW, gb) = (g^T x, column sum of g) for g [E, N], x [E, K] with "
+        "N, K <= 256, any float dtype, in the accumulator dtype (HIP)",
+        pybind11::arg("g"), pybind11::arg("x"),
+        pybind11::arg("want_bias") = false);
+  m.def("linear_wgrad_chunks", &linear_wgrad_chunks,
+        "E-chunks of a linear_wgrad launch: a function of (E, N, K) alone",
+        pybind11::arg("E"), pybind11::arg("N"), pybind11::arg("K"));
+  m.def("linear_wgrad_chunk_rows", &linear_wgrad_chunk_rows,
+        "rows of E in one chunk of a linear_wgrad launch",
+        pybind11::arg("E"), pybind11::arg("N"), pybind11::arg("K"));
   m.def("act_linear_fwd", &act_linear_fwd,
         "y = bf16(silu(h)) W^T + b (HIP)",
         pybind11::arg("h"), pybind11::arg("W"),

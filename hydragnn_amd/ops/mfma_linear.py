@@ -12,7 +12,7 @@ from __future__ import annotations
 import torch
 
 from ._extension import get_extension, use_eager
-from .splitk_linear import SplitKLinear, _splitk_weight_grad
+from .splitk_linear import SplitKLinear, _weight_grad
 
 
 
@@ -59,8 +59,8 @@ class _MFMAMatmul(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 gA = _MFMAMatmul.apply(g, B, False)
             if ctx.needs_input_grad[1]:
-                gB = _splitk_weight_grad(A.reshape(-1, A.shape[-1]),
-                                         g.reshape(-1, g.shape[-1]), 64)
+                gB = _weight_grad(A.reshape(-1, A.shape[-1]),
+                                  g.reshape(-1, g.shape[-1]), 64)
         else:
             # C = A @ B: gA = g @ B^T ; gB = A^T @ g
             if ctx.needs_input_grad[0]:
@@ -71,9 +71,9 @@ class _MFMAMatmul(torch.autograd.Function):
                 # directly (r2 fix: the old .t() silently transposed
                 # the second-order weight grad; square shapes passed
                 # the shape check with WRONG values)
-                gB = _splitk_weight_grad(g.reshape(-1, g.shape[-1]),
-                                         A.reshape(-1, A.shape[-1]),
-                                         64).contiguous()
+                gB = _weight_grad(g.reshape(-1, g.shape[-1]),
+                                  A.reshape(-1, A.shape[-1]),
+                                  64).contiguous()
         return gA, gB, None
 
 
@@ -98,7 +98,7 @@ class _MFMALinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             gx = _MFMAMatmul.apply(g, weight, False)
         if ctx.needs_input_grad[1]:
-            gw = _splitk_weight_grad(x, g, 64)
+            gw = _weight_grad(x, g, 64)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = g.float().sum(0)
         return gx, gw, gb
@@ -138,7 +138,7 @@ class _GemvLinearFn(torch.autograd.Function):
                 gw = (x.float() * g.float()).sum(0, keepdim=True) \
                     .to(torch.bfloat16)
             else:
-                gw = _splitk_weight_grad(x, g, 64)
+                gw = _weight_grad(x, g, 64)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = g.float().sum(0)
         return gx, gw, gb

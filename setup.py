@@ -42,7 +42,8 @@ ext_modules = [
                  "hydragnn_amd/ops/csrc/painn_message.hip",
                  "hydragnn_amd/ops/csrc/edge_affine.hip",
                  "hydragnn_amd/ops/csrc/edge_affine_mfma.hip",
-                 "hydragnn_amd/ops/csrc/act_linear.hip"],
+                 "hydragnn_amd/ops/csrc/act_linear.hip",
+                 "hydragnn_amd/ops/csrc/wgrad.hip"],
         # included files: an edit to one rebuilds the extension (BuildExt)
         depends=["hydragnn_amd/ops/csrc/check_launch.h",
                  "hydragnn_amd/ops/csrc/segment_common.h",
